@@ -1,6 +1,12 @@
 """bench.py -- iLQR iterations/sec (FD + backward + forward) for Hopper H=500.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR then writes what the last timed step left (gains,
+trajectory, costs, selection) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.  --full adds the legs that take
+runs of their own (the cpu_baseline and the speedups derived from it).
 
 A "step" is one ILQR::iterate() (inc/ilqr.h:179-186) of every seed on the
 rank: forward rollout of all line-search candidates + selection, FD sweep at
@@ -8,8 +14,8 @@ all H+1 points, Riccati backward pass, then the one exchange step of the
 multi-GPU design (RCCL all-gather of the per-seed trajectory costs).
 Per GPU: cfg-4's share -- 8 MPC seeds (cfg-3 state + N(0, 0.01^2), splitmix64
 + Box-Muller) x 8 line-search candidates alpha = 2^-i (cfg 3).  value = seed
-iterations/s summed over ranks (weak scaling).  Rank 0 at N=1 also times the
-reference-faithful CPU path on the host cores (cpu_baseline).
+iterations/s summed over ranks (weak scaling).  With --full, rank 0 at N=1 also
+times the reference-faithful CPU path on the host cores (cpu_baseline).
 """
 import argparse
 import json
@@ -261,6 +267,26 @@ class DrySolver:
         return {}
 
 
+def dump_outputs(outdir, rank, arrays):
+    """--dump-outputs: `arrays` ({name: array}) as outdir/<name>.npy in float64
+    (rank 0; the other ranks' own seeds go to <name>.rank<r>.npy)"""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        fn = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(outdir, fn), np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+
+
+def solver_outputs(solver):
+    """what a caller of the timed path holds after its last iterate(): the
+    feedback gains, the nominal trajectory the rollout selected, and every
+    line-search candidate's cost with the selection (a few MB at most)"""
+    K, k = solver.gains()
+    t = solver.traj()
+    costs, sel = solver.costs()
+    return {"gains_K": K, "gains_k": k, "traj_qpos": t.qpos, "traj_qvel": t.qvel, "traj_ctrl": t.ctrl,
+            "candidate_costs": costs, "selected_candidate": sel}
+
+
 CFG5_METRIC = ("iLQR iterations/sec (FD+backward+forward) for Humanoid H=200, fp32 FD + fp64 MFMA Riccati "
                "(BASELINE.json configs[4])")
 FP32_PEAK_TFS = 157.3    # MI355X_MICROARCH.md chip table, FP32 vector
@@ -327,6 +353,8 @@ def run_humanoid_cfg5(args, world, rank, local_rank):
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, "cuda")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, solver_outputs(g))
     kt = {k: {"ms_total": v[0], "launches": v[1], "avg_ms": v[0] / v[1] if v[1] else 0.0} for k, v in g.timing().items()}
     with open(FLOPS_JSON) as f:
         hf = json.load(f)["models"]["humanoid"]
@@ -369,7 +397,7 @@ def run_humanoid_cfg5(args, world, rank, local_rank):
                          "avg_launch_ms": bw_ms, "achieved_tflops": bw_tf, "peak_tflops": FP64_MFMA_PEAK_TFS,
                          "frac": bw_tf / FP64_MFMA_PEAK_TFS, "us_per_step": bw_ms / H * 1e3}},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(args.cpu_budget, H, args.cpu_threads, 1, model="humanoid", cost=ia.HUMANOID_COST)
         out["cpu_baseline"] = cb
         out["speedup_vs_cpu_per_seed"] = value / cb["value"]
@@ -390,7 +418,12 @@ def main():
                     help="seed groups per GPU (ilqg_solver_set_groups): the seeds software-pipelined as G ranges")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU legs out")
+    # everything beyond the headline that takes runs of its own: the CPU legs
+    # (cpu_baseline, child processes on the host cores) and their speedups
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     # how the recursion reads the FD records: the reference's (quirk Q1, the
     # headline) or the corrected Jacobians (ilqg_solver_set_layout; same work)
     ap.add_argument("--layout", choices=("reference", "corrected"), default="reference")
@@ -488,6 +521,13 @@ def main():
     elapsed = max_over_ranks(elapsed, world, dev)
     best_seed = int(best.item())
     gathered = exchange.gather()
+    if args.dump_outputs:
+        # the step's result as its caller sees it: the gathered per-seed costs
+        # and the best seed, and this rank's solver arrays behind them
+        arrays = {"seed_costs": gathered.cpu().numpy(), "best_seed": best_seed}
+        if not args.dry_run:
+            arrays.update(solver_outputs(solver))
+        dump_outputs(args.dump_outputs, rank, arrays)
 
     value = world * S * args.steps / elapsed
     if args.dry_run:
@@ -550,7 +590,7 @@ def main():
         "best_seed": best_seed,
         "exchange": {"costs_gathered": int(gathered.numel()), "best_seed": best_seed},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cb = cpu_baseline(args.cpu_budget, H, args.cpu_threads, A)
         # per seed: one GPU seed-iteration rate vs the reference-faithful CPU iterate()
         out["speedup_vs_cpu_per_seed"] = (value / S) / cb["value"]

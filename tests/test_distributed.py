@@ -169,6 +169,25 @@ def test_bench_launches_ranks_itself_dry_run():
     assert ex["best_seed"] == int(np.argmin(expect))
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as <name>.npy in
+    float64, --steps sets the number of timed steps, and --full is accepted
+    (one rank, no process group)"""
+    import json
+    steps, warm = 3, 1
+    out = tmp_path / "dump"
+    r = _bench(["--gpus", "1", "--dry-run", "--full", "--steps", str(steps), "--warmup", str(warm),
+                "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    g = np.arange(8)
+    expect = np.abs(np.sin(1.0 + g * 0.37 + (steps + warm))) * (1.0 + g)
+    costs, best = np.load(out / "seed_costs.npy"), np.load(out / "best_seed.npy")
+    assert costs.dtype == np.float64 and best.dtype == np.float64
+    assert np.array_equal(costs, expect) and int(best[0]) == int(np.argmin(expect))
+
+
 def test_bench_refuses_world_size_mismatch():
     r = _bench(["--gpus", "4", "--dry-run", "--steps", "1", "--warmup", "0"],
                env_extra={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})

@@ -8,7 +8,7 @@
 #   tests[=LIB]          full -m gpu suite (optionally against ILQG_LIB=LIB)
 #   testk=EXPR           -m gpu tests selected by -k EXPR
 #   smoke                __graft_entry__.smoke()
-#   bench                default bench line (with the CPU baseline)
+#   bench                default bench line with the CPU baseline (bench.py --full)
 #   ab=NAME[,ENV=V...]   REPS (default 3) bench lines, 20 steps, no CPU leg;
 #                        ENV=V pairs may include ILQG_LIB=...
 #   cfg5[=NAME,ENV=V...] REPS cfg-5 humanoid bench lines (ENV may include ILQG_LIB=...)
@@ -49,7 +49,7 @@ for step in "$@"; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || fail smoke $OUT/smoke.log
     tail -1 $OUT/smoke.log ;;
   bench)
-    timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
+    timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
     cat $OUT/bench.json ;;
   ab)
     name=${arg%%,*}; envs=""; [[ $arg == *,* ]] && envs=${arg#*,}; envs=${envs//,/ }
@@ -66,7 +66,7 @@ for step in "$@"; do
       summ $f "cfg5 $name#$r"
     done ;;
   cfg5cpu)
-    timeout -k 10 600 python bench.py --workload humanoid_cfg5 --steps 5 > $OUT/cfg5_bench.json 2> $OUT/cfg5_bench.err \
+    timeout -k 10 600 python bench.py --workload humanoid_cfg5 --steps 5 --full > $OUT/cfg5_bench.json 2> $OUT/cfg5_bench.err \
       || fail cfg5cpu $OUT/cfg5_bench.err
     summ $OUT/cfg5_bench.json "cfg5 (with cpu_baseline)" ;;
   cfg5trace)
