@@ -325,9 +325,14 @@ __device__ __forceinline__ double readlane_f64(double x, int l) {
 // (lane k's products, read across the wave with v_readlane), the row's dot
 // product with temp ascending from +0, its subtraction from the input entry,
 // the division by the updated diagonal.  The factor is the same bit for bit
-// (tests/test_gpu_parity.py::test_ldlt_reg_matches_lds); a NaN or an all-zero
-// diagonal (ldlt_factor's early exit) takes ldlt_factor_wave_t + ldlt_perm.
-// Writes the lower triangle and diagonal of mat, transp and perm.
+// (tests/test_gpu_parity.py::test_ldlt_reg_matches_lds; with tied, zero,
+// denormal and NaN keys tests/test_riccati_cases.py::test_mfma_engine); a NaN
+// or an all-zero diagonal (ldlt_factor's early exit) takes ldlt_factor_wave_t
+// + ldlt_perm.
+// Writes the lower triangle and diagonal of mat, and perm.  transp is NOT
+// written on the register path (only the NaN / all-zero fallback writes it):
+// it keeps whatever an earlier step left, and perm alone carries the pivot
+// order to the solves.
 // (replay: the replay even without equal keys, for the test)
 template <int N>
 __device__ inline void ldlt_factor_reg_t(double* mat, int* transp, int* perm, double* temp, int lane,

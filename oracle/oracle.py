@@ -87,6 +87,7 @@ class Lib:
         L.ora_set_layout.argtypes = [ctypes.c_int]
         L.ora_ilqr_backwardPass_v0.argtypes = [ctypes.c_void_p, _dp, _dp]
         L.ora_ilqr_iterate_v0.argtypes = [ctypes.c_void_p, _dp, _dp]
+        L.ora_state_diff.argtypes = [ctypes.c_void_p] + [_dp] * 5
         L.ora_riccati_step.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                        _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         if hasattr(L, "ref_calcMJDerivatives"):
@@ -234,6 +235,14 @@ def calc_derivatives(model: OModel, d: OData, cost_fn: str = "ora_cost_pendulum"
     return deriv
 
 
+def state_diff(model: OModel, qa, va, qb, vb):
+    """x_a (-) x_b in the tangent space (2 nv entries): ora_state_diff, the c of a Riccati step"""
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in (qa, va, qb, vb)]
+    dx = np.zeros(2 * model.nv)
+    model.lib.L.ora_state_diff(model.m, *(x.ctypes.data_as(_dp) for x in a), dx.ctypes.data_as(_dp))
+    return dx
+
+
 class OILQR:
     """ora_ilqr: restatement of ILQR<nv,nu,N> (inc/ilqr.h)."""
 
@@ -325,9 +334,11 @@ class OILQR:
         st = ctypes.cast(self.s, ctypes.POINTER(S)).contents
         return OData(self.model, handle=st.dArray[n])
 
-    def backward_from_records(self, deriv):
+    def backward_from_records(self, deriv, V0=None, v0=None):
         """backwardPass (initV + the recursion, inc/ilqr.h:100-107,133-176) over
-        the given FD records (P x D) instead of the oracle's own sweep"""
+        the given FD records (P x D) instead of the oracle's own sweep; with
+        V0 (nx x nx, column-major) and v0 the recursion starts from them
+        (the overridden initV of backward_pass_v0)"""
         class S(ctypes.Structure):
             _fields_ = [("m", ctypes.c_void_p), ("N", ctypes.c_int), ("nv", ctypes.c_int), ("nu", ctypes.c_int),
                         ("nx", ctypes.c_int), ("D", ctypes.c_int), ("d", ctypes.c_void_p),
@@ -340,8 +351,13 @@ class OILQR:
         np.ctypeslib.as_array(st.deriv, shape=(P, st.D))[:] = rec
         calc = st.calc
         st.calc = self.lib.fnptr("ora_calc_none").value
+        if (V0 is None) != (v0 is None):
+            raise ValueError("V0 and v0 go together")
         try:
-            self.lib.L.ora_ilqr_backwardPass(self.s)
+            if V0 is None:
+                self.lib.L.ora_ilqr_backwardPass(self.s)
+            else:
+                self.backward_pass_v0(V0, v0)
         finally:
             st.calc = calc
 

@@ -408,7 +408,12 @@ def test_ldlt_reg_matches_lds(ia, monkeypatch):
     ldlt_factor_wave_t), with its pivot order from ranks of distinct keys or
     from the scan replayed (ILQG_LDLT_REG=2): the same operations in the same
     order, so K, k, V, v agree bit for bit (cfg 5's state, H = 200, after two
-    iterations)"""
+    iterations).  These are physical Quu matrices: whatever equal |diagonal|
+    keys the symmetric standing pose presents, the three variants are compared
+    with each other only, so a first-hit rule that is wrong in all of them
+    passes here.  Crafted ties (at the maximum too), zero, denormal and NaN
+    pivots, with step 1 anchored to the oracle at zero difference, are covered
+    by tests/test_riccati_cases.py::test_mfma_engine."""
     m = ia.Model.load(model_path("humanoid"))
     st = m.reset_state(1)
     st.qpos[0, 2] = 1.4
