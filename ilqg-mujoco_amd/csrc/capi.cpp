@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -314,6 +315,15 @@ struct ilqg_solver {
   int layout = ILQG_LAYOUT_REFERENCE;
   bool vinit_pending = false;  // the next recursion starts from the uploaded V / v
   RicFlags flags() const { return RicFlags{layout, vinit_pending ? 1 : 0}; }
+  // control limits (ilqg_solver_set_ctrl_limits): lo[nu] | hi[nu] on the device
+  // for the clamped rollout and the boxed recursion, whose per-(seed, point)
+  // clamped sets and QP reports land in cl_mask / cl_info; cl_valid: the last
+  // backward pass was a boxed one (ilqg_solver_get_clamped reads zeros otherwise)
+  bool limits = false, cl_valid = false;
+  std::vector<double> host_lim;
+  DevBuf ulim, cl_mask, cl_info;
+  // the fused sweep streams the bit-exact, unboxed recursion behind the fp64 sweep
+  void choose_fused();
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[ILQG_NKERNEL];
   std::vector<hipEvent_t> event_pool;
@@ -392,6 +402,11 @@ struct ilqg_solver {
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 };
+
+static bool fused_ok(const ilqg_model* m);
+void ilqg_solver::choose_fused() {
+  fused = !limits && riccati == ILQG_RICCATI_EXACT && fdprec == ILQG_FD_F64 && fused_ok(model) && sync.p;
+}
 
 static std::vector<double> pack_cost(const HostModel& m, const ilqg_cost* c) {
   const int nq = m.nq, nv = m.nv, nu = m.nu;
@@ -473,6 +488,17 @@ int ilqg_model_sizes(const ilqg_model* m, int* s) {
 int ilqg_model_timestep(const ilqg_model* m, double* dt) {
   if (!m || !dt) return fail(ILQG_ERR_ARG, "null argument");
   *dt = m->host.opt_timestep;
+  return ILQG_OK;
+}
+
+int ilqg_model_ctrlrange(const ilqg_model* m, double* lo, double* hi) {
+  if (!m || !lo || !hi) return fail(ILQG_ERR_ARG, "null argument");
+  const HostModel& h = m->host;
+  for (int a = 0; a < h.nu; a++) {
+    const bool lim = h.actuator_ctrllimited[a] != 0;
+    lo[a] = lim ? h.actuator_ctrlrange[2 * a] : -INFINITY;
+    hi[a] = lim ? h.actuator_ctrlrange[2 * a + 1] : INFINITY;
+  }
   return ILQG_OK;
 }
 
@@ -900,6 +926,13 @@ static TrajDev toff(TrajDev t, size_t pts, const HostModel& h) {
   return TrajDev{t.time + pts, t.qpos + pts * h.nq, t.qvel + pts * h.nv, t.warm + pts * h.nv, t.ctrl + pts * h.nu};
 }
 
+// with control limits the rollout must be a kernel that has a clamped variant
+static int limits_rollout_check(const ilqg_solver* s) {
+  if (s->limits && !rollout_clamp_supported())
+    return fail(ILQG_ERR_UNSUPPORTED, "control limits: the rollout kernel selected by ILQG_DUAL=0 has no clamped variant");
+  return ILQG_OK;
+}
+
 // rollout of every (seed, alpha) candidate of the range, then selection + setDInit
 static hipError_t rollout_launch(ilqg_solver* s, const SeedRange& r, RollChunk ch);
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st);
@@ -941,6 +974,7 @@ static hipError_t rollout_launch(ilqg_solver* s, const SeedRange& r, RollChunk c
   const double* xf = s->xfrc_applied.as<double>() + s0 * 6 * h.nbody;
   double* cc = s->cost_cand.as<double>() + s0 * A;
   if (ch.n_hi >= 0) ch.carry = toff(s->tview(s->carry), s0 * A, h);
+  if (s->limits) ch.ulim = s->ulim.as<double>();
   return s->timed(0, [&] {
     return launch_rollout_coop(m->dm, m->Lc, m->C, m->X, r.ns, s->A, s->P, nom, outv, multi ? 1 : 0, K, k,
                                s->alphas.as<double>(), di, qa, xf, 0, s->cview(), cc, r.st, ch);
@@ -1100,6 +1134,7 @@ static int iterate_pipelined(ilqg_solver* s, int rank = 0, int world = 1, bool b
 int ilqg_forward_sharded(ilqg_solver* s, int rank, int world) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
   if (world < 1 || rank < 0 || rank >= world) return fail(ILQG_ERR_ARG, "rank outside [0, world)");
+  if (int rc = limits_rollout_check(s)) return rc;
   if (s->pipe_chunk <= 0 || !s->pipe_flat || s->fused)
     return fail(ILQG_ERR_UNSUPPORTED, "point sharding rides the pipelined iterate (one candidate per seed, the "
                                       "unfused sweep: fp32 FD or the MFMA recursion, flat chunks)");
@@ -1121,6 +1156,7 @@ int ilqg_point_owners(int npoint, int chunk, int world, int* owner) {
 
 int ilqg_forward(ilqg_solver* s) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
+  if (int rc = limits_rollout_check(s)) return rc;
   s->grp_join = true;
   HIPCHK(forward_range(s, whole(s)));
   return ILQG_OK;
@@ -1304,7 +1340,16 @@ int ilqg_backward(ilqg_solver* s) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
   s->grp_join = true;
   const ilqg_model* m = s->model;
+  s->cl_valid = s->limits;
   HIPCHK(s->timed(4, [&] {
+    // control limits: the boxed recursion (set_ctrl_limits keeps the MFMA engine out)
+    if (s->limits)
+      return launch_backward_box(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
+                                 s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
+                                 s->flags(),
+                                 BoxDev{s->ulim.as<double>(), s->ulim.as<double>() + m->host.nu,
+                                        s->cl_mask.as<unsigned>(), s->cl_info.as<unsigned>()},
+                                 s->stream);
     if (s->riccati == ILQG_RICCATI_MFMA)
       return launch_backward_mfma(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
                                   s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
@@ -1349,6 +1394,7 @@ static int iterate_groups(ilqg_solver* s) {
     r.st = s->grp_fd[g];
     HIPCHK(hipStreamWaitEvent(r.st, s->grp_sel[g], 0));
     // the sweep with the group's recursion streamed behind it: one launch
+    s->cl_valid = false;
     HIPCHK(s->timed(5, [&] { return fused_launch(s, r, 1); }, r.st));
     HIPCHK(hipEventRecord(s->grp_done[g], r.st));
   }
@@ -1359,12 +1405,14 @@ static int iterate_groups(ilqg_solver* s) {
 
 int ilqg_iterate(ilqg_solver* s) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
+  if (int rc = limits_rollout_check(s)) return rc;
   if (s->ngroups > 1 && s->fused) return iterate_groups(s);
   if (!s->fused && s->pipe_chunk > 0) return iterate_pipelined(s);
   int rc = ilqg_forward(s);
   if (rc) return rc;
   if (s->fused) {
     // FD sweep with the Riccati recursion of every seed streamed behind it (one launch)
+    s->cl_valid = false;
     HIPCHK(s->timed(5, [&] { return fused_launch(s, whole(s), 1); }));
     s->vinit_pending = false;
     return ILQG_OK;
@@ -1456,6 +1504,71 @@ int ilqg_solver_set_mu(ilqg_solver* s, double mu) {
   return ILQG_OK;
 }
 
+int ilqg_solver_set_ctrl_limits(ilqg_solver* s, const double* lo, const double* hi) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if ((lo == nullptr) != (hi == nullptr)) return fail(ILQG_ERR_ARG, "lo and hi: both arrays, or both NULL");
+  const HostModel& h = s->model->host;
+  const size_t nu = h.nu;
+  if (!lo) {  // off: the solver as it was created (the fused sweep where it applies)
+    HIPCHK(s->sync_all());
+    s->limits = false;
+    s->cl_valid = false;
+    s->choose_fused();
+    return ILQG_OK;
+  }
+  for (size_t a = 0; a < nu; a++) {
+    if (lo[a] != lo[a] || hi[a] != hi[a]) return fail(ILQG_ERR_ARG, "control limits: NaN");
+    if (lo[a] > hi[a]) return fail(ILQG_ERR_ARG, "control limits: lo > hi");
+  }
+  if (s->riccati == ILQG_RICCATI_MFMA)
+    return fail(ILQG_ERR_UNSUPPORTED, "control limits: the MFMA Riccati engine has no boxed variant "
+                                      "(ilqg_solver_set_riccati(s, ILQG_RICCATI_EXACT) first)");
+  if (s->ngroups > 1)
+    return fail(ILQG_ERR_UNSUPPORTED, "control limits: seed groups stream the unboxed recursion "
+                                      "(ilqg_solver_set_groups(s, 1) first)");
+  if (backward_box_lds_bytes(h.nv, h.nu) > kMaxLds)
+    return fail(ILQG_ERR_UNSUPPORTED, "control limits: the boxed Riccati workspace exceeds one CU's 160 KB of LDS");
+  HIPCHK(s->sync_all());  // launches already enqueued keep the limits they were given
+  if (!s->ulim.p) {
+    HIPCHK(s->ulim.alloc(2 * nu * 8));
+    HIPCHK(s->cl_mask.alloc((size_t)s->S * s->P * sizeof(unsigned)));
+    HIPCHK(s->cl_info.alloc((size_t)s->S * s->P * sizeof(unsigned)));
+  }
+  s->host_lim.assign(lo, lo + nu);
+  s->host_lim.insert(s->host_lim.end(), hi, hi + nu);
+  HIPCHK(hipMemcpy(s->ulim.p, s->host_lim.data(), 2 * nu * 8, hipMemcpyHostToDevice));
+  s->limits = true;
+  s->fused = false;  // rollout, select, sweep, then the boxed ilqg_backward
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* enabled) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  const size_t nu = s->model->host.nu;
+  for (size_t a = 0; a < nu; a++) {
+    if (lo) lo[a] = s->limits ? s->host_lim[a] : -INFINITY;
+    if (hi) hi[a] = s->limits ? s->host_lim[nu + a] : INFINITY;
+  }
+  if (enabled) *enabled = s->limits ? 1 : 0;
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_clamped(ilqg_solver* s, unsigned* mask, unsigned* info) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  HIPCHK(s->sync_all());
+  const size_t n = (size_t)s->S * s->P;
+  const bool have = s->cl_valid && s->cl_mask.p;
+  if (mask) {
+    if (have) HIPCHK(hipMemcpy(mask, s->cl_mask.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    else std::fill(mask, mask + n, 0u);
+  }
+  if (info) {
+    if (have) HIPCHK(hipMemcpy(info, s->cl_info.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    else std::fill(info, info + n, 0u);
+  }
+  return ILQG_OK;
+}
+
 int ilqg_solver_set_stream(ilqg_solver* s, void* stream) {
   if (!s) return fail(ILQG_ERR_ARG, "null solver");
   HIPCHK(s->sync_all());
@@ -1495,12 +1608,15 @@ int ilqg_solver_set_riccati(ilqg_solver* s, int mode) {
   if (mode == ILQG_RICCATI_MFMA) {
     if (!backward_mfma_supported(h.nv, h.nu))
       return fail(ILQG_ERR_UNSUPPORTED, "MFMA Riccati: nu <= 32, 2 nv + 1 <= 256, FD record <= 4096 doubles, LDS <= 160 KB");
+    if (s->limits)
+      return fail(ILQG_ERR_UNSUPPORTED, "MFMA Riccati: no boxed variant; switch the control limits off first "
+                                        "(ilqg_solver_set_ctrl_limits(s, NULL, NULL))");
   }
   HIPCHK(s->sync_all());
   s->riccati = mode;
   // the fused sweep streams the bit-exact recursion; the MFMA one runs after a
   // plain sweep (its workspace -- the hand-off block -- is allocated either way)
-  s->fused = mode == ILQG_RICCATI_EXACT && s->fdprec == ILQG_FD_F64 && fused_ok(s->model) && s->sync.p;
+  s->choose_fused();
   return ILQG_OK;
 }
 
@@ -1510,7 +1626,7 @@ int ilqg_solver_set_fd_precision(ilqg_solver* s, int prec) {
   HIPCHK(s->sync_all());
   s->fdprec = prec;
   // the fused sweep is the fp64 one: fp32 FD runs the two-kernel sweep, then the recursion
-  s->fused = s->riccati == ILQG_RICCATI_EXACT && prec == ILQG_FD_F64 && fused_ok(s->model) && s->sync.p;
+  s->choose_fused();
   return ILQG_OK;
 }
 
@@ -1534,6 +1650,9 @@ int ilqg_solver_set_value(ilqg_solver* s, const double* V, const double* v) {
 int ilqg_solver_set_groups(ilqg_solver* s, int ngroups) {
   if (!s || ngroups < 1 || ngroups > ilqg_solver::kMaxGroups || ngroups > s->S)
     return fail(ILQG_ERR_ARG, "ngroups must be in 1 .. min(4, nseed)");
+  if (ngroups > 1 && s->limits)
+    return fail(ILQG_ERR_UNSUPPORTED, "seed groups stream the unboxed recursion; switch the control limits off first "
+                                      "(ilqg_solver_set_ctrl_limits(s, NULL, NULL))");
   HIPCHK(s->sync_all());
   s->free_groups();
   s->grp_join = true;

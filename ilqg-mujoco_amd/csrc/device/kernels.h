@@ -29,6 +29,9 @@ struct RollChunk {
   // double-buffered in LDS past the team's workspace, the next point's copied
   // by the helper wave while the primary runs the constraint solve
   int dbuf = 0;
+  // control limits (ilqg_solver_set_ctrl_limits): lo[nu] then hi[nu] on the
+  // device, read by the clamped rollout kernels only; null = no limits
+  const double* ulim = nullptr;
 };
 
 // device cost descriptor (all 9 arrays present, zero where unused)
@@ -72,6 +75,20 @@ hipError_t launch_select(const DevModel& m, int S, int A, int P, int mode, int c
 hipError_t launch_backward(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
                            double* K, double* k, double* V, double* v, RicFlags fl, hipStream_t st);
 size_t backward_lds_bytes(int nv, int nu);
+// the boxed recursion (ilqg_solver_set_ctrl_limits; riccati.h backward_seed
+// with BOX): each step's feed-forward solves min 1/2 k'(-Mm)k + col'k over
+// lo - u* <= k <= hi - u* by projected Newton, the clamped controls' gain rows
+// are zero.  lo, hi: nu doubles each on the device; mask, info: [S][P] words
+// (bit a of mask = control a clamped; info = QP iterations, bit 31 = fallback)
+struct BoxDev {
+  const double* lo = nullptr;
+  const double* hi = nullptr;
+  unsigned* mask = nullptr;
+  unsigned* info = nullptr;
+};
+hipError_t launch_backward_box(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
+                               double* K, double* k, double* V, double* v, RicFlags fl, BoxDev bx, hipStream_t st);
+size_t backward_box_lds_bytes(int nv, int nu);
 // the same recursion with the matrix products on the fp64 matrix cores
 // (riccati_mfma.h): one 8-wave workgroup per seed; agrees with the oracle to
 // rounding (the product sums run in the matrix core's order)
@@ -159,6 +176,9 @@ hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const coop:
                                int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit,
                                const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost,
                                double* cost_cand, hipStream_t st, RollChunk ch = RollChunk{});
+// whether the rollout kernel this process selects (ILQG_DUAL) has a clamped
+// variant (RollChunk.ulim): launch_rollout_coop refuses limits otherwise
+bool rollout_clamp_supported();
 // n independent states, one wavefront each: nstep mj_step (in place)
 hipError_t launch_step_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
                             TrajDev stt, int n, int nstep, const double* qfrc_applied, const double* xfrc_applied,

@@ -24,7 +24,9 @@ namespace ilqg {
 namespace {
 
 __device__ inline void rollout_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, int wave, auto split, auto lowreg) {
+                                int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, int wave, auto split, auto lowreg, auto clamp) {
+  // clamp (the *_lim kernels, launched while control limits are set): the
+  // control law's output confined to [ch.ulim[i], ch.ulim[nu + i]]
   // wave < 0: one-wave team; 0/1: primary/helper wave of a two-wave team (step_dual)
   const bool prim = wave <= 0;
   STAMP_INIT();
@@ -126,7 +128,13 @@ __device__ inline void rollout_body(const auto& m, const auto& L, const auto& C,
           }
         }
         for (; j < nx; j++) t += rK[i + j * nu] * dx[j];
-        ctrl[i] = (t + alpha * rk[i]) + ru[i];
+        double cv = (t + alpha * rk[i]) + ru[i];
+        if constexpr (decltype(clamp)::value) {
+          // (+-0 and NaN pass through unchanged); the record and the cost take the clamped value
+          const double lo = ch.ulim[i], hi = ch.ulim[nu + i];
+          cv = cv < lo ? lo : (cv > hi ? hi : cv);
+        }
+        ctrl[i] = cv;
       }
       TSYNC();
     }
@@ -230,7 +238,7 @@ __global__ __launch_bounds__(TEAM) void k_rollout_coop(DevModel mg, WsLayout L, 
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch, -1, std::false_type{}, std::false_type{});
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch, -1, std::false_type{}, std::false_type{}, std::false_type{});
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
@@ -242,7 +250,7 @@ __global__ __launch_bounds__(TEAM) void k_rollout_s(DevModel mg, int S, int A, i
   Team T = make_team(L, C);
   SM m;
   stage_model_sep(mg, T, m);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch, -1, std::false_type{}, std::false_type{});
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch, -1, std::false_type{}, std::false_type{}, std::false_type{});
 }
 
 // two-wave teams (step_dual): 128 threads per (seed, candidate).  MT: DevModel,
@@ -255,7 +263,19 @@ __global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop(DevModel mg, WsLayou
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
   rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
-               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{});
+               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
+               std::false_type{});
+}
+// k_rollout2_coop with the control law clamped to the solver's control limits (RollChunk.ulim)
+template <class MT>
+__global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop_lim(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
+  Team T = make_team(L, C);
+  MT m;
+  CoopAux X;
+  stage_model(mg, Xg, L, C, T, m, X);
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
+               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
+               std::true_type{});
 }
 // three-wave teams for the compile-time register-row models (step_dual_split),
 // two-wave otherwise
@@ -271,7 +291,20 @@ __global__ __launch_bounds__(3 * TEAM) void k_rollout2_s(DevModel mg, int S, int
   stage_model_sep(mg, T, m);
   rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
                passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
-               std::false_type{});
+               std::false_type{}, std::false_type{});
+}
+// k_rollout2_s with the control law clamped to the solver's control limits (RollChunk.ulim)
+template <class SM, class SX>
+__global__ __launch_bounds__(3 * TEAM) void k_rollout2_s_lim(DevModel mg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
+  static constexpr WsLayout L = make_layout(SM{}, SX::npair, true);
+  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
+  static constexpr SX X{};
+  Team T = make_team(L, C);
+  SM m;
+  stage_model_sep(mg, T, m);
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
+               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
+               std::false_type{}, std::true_type{});
 }
 
 // ---- batch physics (ilqg_step_batch / ilqg_forward_batch): one wavefront per state
@@ -415,6 +448,29 @@ hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const CoopL
                                hipStream_t st, RollChunk ch) {
   const size_t lds = rollout_lds(coop_lds_bytes(L, C));
   hipError_t e;
+  // control limits: the clamped variants of the default kernels (k_rollout2_s,
+  // k_rollout2_coop); the passive constructor rollout has no control law
+  const bool lim = ch.ulim != nullptr && !passive;
+  if (lim && !use_dual()) return hipErrorNotSupported;
+  if (lim) {
+#define ILQG_CASE(id, SMT, SXT)                                                                                 \
+  case id: {                                                                                                    \
+    const size_t lds2 = rollout_lds(coop_lds_bytes(make_layout(stat::SMT{}, stat::SXT::npair, true), C));       \
+    e = allow_lds(k_rollout2_s_lim<stat::SMT, stat::SXT>, lds2);                                                \
+    if (e != hipSuccess) return e;                                                                              \
+    hipLaunchKernelGGL((k_rollout2_s_lim<stat::SMT, stat::SXT>), dim3(S * A),                                   \
+                       dim3(rollout_waves<stat::SMT>() * TEAM), lds2, st, m, S, A, P,                            \
+                       nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, \
+                       cost_cand, ch);                                                                              \
+    return hipGetLastError();                                                                                   \
+  }
+    switch (m.static_id) {
+      ILQG_STATIC_MODELS(ILQG_CASE)
+      default:
+        break;
+    }
+#undef ILQG_CASE
+  }
   if (use_dual()) {
 #define ILQG_CASE(id, SMT, SXT)                                                                                 \
   case id: {                                                                                                    \
@@ -457,6 +513,21 @@ hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const CoopL
                           : reinterpret_cast<const void*>(k_rollout2_coop<DevModel>);
     e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
     if (e != hipSuccess) return e;
+    if (lim) {
+      const void* kl = nv27 ? reinterpret_cast<const void*>(k_rollout2_coop_lim<DevModelNV<27>>)
+                            : reinterpret_cast<const void*>(k_rollout2_coop_lim<DevModel>);
+      e = hipFuncSetAttribute(kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
+      if (e != hipSuccess) return e;
+      if (nv27)
+        hipLaunchKernelGGL(k_rollout2_coop_lim<DevModelNV<27>>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S,
+                           A, P, nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive,
+                           cost, cost_cand, ch);
+      else
+        hipLaunchKernelGGL(k_rollout2_coop_lim<DevModel>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S, A, P,
+                           nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost,
+                           cost_cand, ch);
+      return hipGetLastError();
+    }
     if (nv27)
       hipLaunchKernelGGL(k_rollout2_coop<DevModelNV<27>>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S, A,
                          P, nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost,
@@ -486,6 +557,8 @@ hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const CoopL
                      out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch);
   return hipGetLastError();
 }
+
+bool rollout_clamp_supported() { return use_dual(); }
 
 hipError_t launch_select(const DevModel& m, int S, int A, int P, int mode, int copy_cand, const double* cost_cand,
                          int* sel, double* cost_sel, TrajDev cand, TrajDev nominal, TrajDev dinit, hipStream_t st) {

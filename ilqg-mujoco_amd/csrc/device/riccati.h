@@ -553,14 +553,149 @@ __device__ inline void ldlt_solve_bcast_t(const double* Lm, const int* perm, con
     const bool h1 = e1 < (n), h2 = e2 < (n);             \
     const int f1 = h1 ? e1 : e0, f2 = h2 ? e2 : e0;
 
-template <int NV_, int NU_, class MD>
+// ---- the boxed step (BOX instances of backward_seed; the reference has no
+// counterpart).  Trip bounds of its two loops, both compile-time: a step that
+// exhausts either takes the fallback, so no input can make the kernel wait.
+constexpr int BOX_MAXIT = 32;   // projected-Newton iterations
+constexpr int BOX_MAXLS = 24;   // Armijo halvings (0.6^24 ~ 5e-6 of the Newton step)
+constexpr double BOX_ARMIJO = 0.1, BOX_SHRINK = 0.6;
+// extra LDS of a BOX instance, in doubles: Mm's copy and seven nu-vectors
+__host__ __device__ constexpr size_t box_lds_doubles(size_t nu) { return nu * nu + 7 * nu; }
+// a wave-uniform flag as a scalar: every lane computed the same value from LDS
+__device__ __forceinline__ int box_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double box_clip(double c, double lo, double hi) { return c < lo ? lo : (c > hi ? hi : c); }
+// LDS of one boxed step.  Mo: Mm as stage 3 built it (Mm itself is factored in
+// place); bl, bh: the bounds on k; x: the iterate; gr: col - Mo x; xt: the
+// Newton target; xc, gc: the line search's candidate and its gradient
+struct BoxLds {
+  double *Mo, *bl, *bh, *x, *gr, *xt, *xc, *gc;
+};
+// out = col - Mo in: lane a's row, ascending b
+__device__ inline void box_grad(int nu, const double* Mo, const double* col, const double* in, double* out, int tid) {
+  if (tid < nu) {
+    double sm = 0;
+    for (int b = 0; b < nu; b++) sm += Mo[tid + b * nu] * in[b];
+    out[tid] = col[tid] - sm;
+  }
+}
+// min 1/2 k'(-Mo)k + col'k over bl <= k <= bh by projected Newton (Tassa,
+// Mansard & Todorov 2014) from the clamped unconstrained k (kl), one wavefront.
+// The clamped set is the controls at a bound whose gradient points outward; the
+// Newton target solves the free block -- Mm rebuilt from Mo with every clamped
+// row and column replaced by a -1 diagonal entry, the bounds' contribution on
+// the right-hand side -- and the step is backtracked with projection until
+// Armijo's condition holds.  The iteration ends when a full, unprojected step
+// leaves the clamped set unchanged (the iterate is then that set's stationary
+// point exactly, not to a gradient tolerance), or every control is clamped.
+// Every decision is computed by all lanes from the same LDS values in the same
+// order and passed through box_uni: the branches around the barriers are
+// wave-uniform.  Returns the clamped set in *mask and the iteration count, or
+// -1 for the fallback (a free-block pivot >= 0 or NaN, no acceptable step, or
+// BOX_MAXIT reached).  On a regular return with a free control, Mm / trn hold
+// the factor of the final set's matrix.
+__device__ inline int box_solve(int nu, const BoxLds& L, double* Mm, const double* col, const double* kl, int* trn,
+                                double* temp, int tid, unsigned* mask_out) {
+  const unsigned full = nu >= 32 ? ~0u : ((1u << nu) - 1u);
+  if (tid < nu) L.x[tid] = box_clip(kl[tid], L.bl[tid], L.bh[tid]);
+  wave_sync();
+  unsigned prev = 0;
+  int lastfull = 0, state = 0, iters = 0;  // state: 0 iterating, 1 done, -1 fallback
+  unsigned mask = 0;
+#pragma unroll 1
+  for (int it = 0; it < BOX_MAXIT; it++) {
+    if (box_uni(state != 0)) break;
+    box_grad(nu, L.Mo, col, L.x, L.gr, tid);
+    wave_sync();
+    mask = 0;
+    for (int a = 0; a < nu; a++) {
+      const double xa = L.x[a], ga = L.gr[a];
+      if ((xa == L.bl[a] && ga > 0) || (xa == L.bh[a] && ga < 0)) mask |= 1u << a;
+    }
+    mask = (unsigned)box_uni((int)mask);
+    if (box_uni(mask == full || (it > 0 && lastfull && mask == prev))) {
+      state = 1;
+      break;
+    }
+    // the free block's matrix and right-hand side
+    for (int e = tid; e < nu * nu; e += BW_THREADS) {
+      const int a = e % nu, b = e / nu;
+      const bool cl = ((mask >> a) | (mask >> b)) & 1u;
+      Mm[e] = cl ? (a == b ? -1.0 : 0.0) : L.Mo[e];
+    }
+    if (tid < nu) {
+      double sm = col[tid];
+      if ((mask >> tid) & 1u) {
+        sm = -L.x[tid];
+      } else {
+        for (int b = 0; b < nu; b++)
+          if ((mask >> b) & 1u) sm -= L.Mo[tid + b * nu] * L.x[b];
+      }
+      L.xt[tid] = sm;
+    }
+    wave_sync();
+    ldlt_factor_wave(nu, Mm, trn, temp, tid);
+    // -Mm_ff must be positive definite: every pivot of the factor negative
+    int ok = 1;
+    for (int a = 0; a < nu; a++) ok &= Mm[a + a * nu] < 0 ? 1 : 0;
+    if (box_uni(!ok)) {
+      state = -1;
+      break;
+    }
+    if (tid == 0) ldlt_solve(nu, Mm, trn, L.xt);
+    wave_sync();
+    if (tid < nu && ((mask >> tid) & 1u)) L.xt[tid] = L.x[tid];
+    wave_sync();
+    // f(x) = 1/2 x'(-Mo)x + col'x = 1/2 sum x_a (gr_a + col_a)
+    double f0 = 0;
+    for (int a = 0; a < nu; a++) f0 += L.x[a] * (L.gr[a] + col[a]);
+    f0 *= 0.5;
+    double step = 1.0;
+    int acc = 0;
+#pragma unroll 1
+    for (int ls = 0; ls < BOX_MAXLS; ls++) {
+      if (box_uni(acc)) break;
+      // (the full step is the target itself: x + (xt - x) may round to its neighbour)
+      if (tid < nu)
+        L.xc[tid] = box_clip(step == 1.0 ? L.xt[tid] : L.x[tid] + step * (L.xt[tid] - L.x[tid]), L.bl[tid], L.bh[tid]);
+      wave_sync();
+      box_grad(nu, L.Mo, col, L.xc, L.gc, tid);
+      wave_sync();
+      double fc = 0, dec = 0;
+      for (int a = 0; a < nu; a++) {
+        fc += L.xc[a] * (L.gc[a] + col[a]);
+        dec += L.gr[a] * (L.xc[a] - L.x[a]);
+      }
+      fc *= 0.5;
+      acc = box_uni(fc - f0 <= BOX_ARMIJO * dec ? 1 : 0);  // a NaN never accepts
+      if (!acc) step *= BOX_SHRINK;
+      wave_sync();  // xc, gc are rewritten by the next trial
+    }
+    if (box_uni(!acc)) {
+      state = -1;
+      break;
+    }
+    int fullstep = step == 1.0 ? 1 : 0;
+    for (int a = 0; a < nu; a++) fullstep &= L.xc[a] == L.xt[a] ? 1 : 0;
+    lastfull = box_uni(fullstep);
+    prev = mask;
+    wave_sync();
+    if (tid < nu) L.x[tid] = L.xc[tid];
+    wave_sync();
+    iters++;
+  }
+  *mask_out = mask;
+  return box_uni(state) == 1 ? iters : -1;
+}
+
+template <int NV_, int NU_, bool BOX = false, class MD>
 __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, int P, double dt, double mu,
                                      const double* deriv, int Ds, TrajDev tr, double* Kg, double* kg, double* Vg,
                                      double* vg, int s, int tid, double* sh, const unsigned* done, unsigned target,
-                                     unsigned* fault, RicFlags fl) {
+                                     unsigned* fault, RicFlags fl, BoxDev bx = BoxDev{}) {
 #ifndef ILQG_RIC_LDS
   // bundled small models: the register/exchange formulation (riccati_reg.h)
-  if constexpr (RicReg<NV_, NU_>::ok) {
+  // (a BOX instance is always the LDS formulation below)
+  if constexpr (!BOX && RicReg<NV_, NU_>::ok) {
     if (nq == NV_) {
       backward_seed_reg<NV_, NU_>(m, P, dt, mu, deriv, Ds, tr, Kg, kg, Vg, vg, s, tid, sh, done, target, fault, fl);
       return;
@@ -618,6 +753,19 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
   double* col = kR + nu;
   double* r = col + nu;
   double* dl = r + nu;  // FD record of the current step (prefetched), D doubles when pref
+  BoxLds bL{};
+  if constexpr (BOX) {
+    static_assert(BOX_MAXIT > 0 && BOX_MAXLS > 0, "compile-time trip bounds");
+    bL.Mo = dl;
+    bL.bl = bL.Mo + nu * nu;
+    bL.bh = bL.bl + nu;
+    bL.x = bL.bh + nu;
+    bL.gr = bL.x + nu;
+    bL.xt = bL.gr + nu;
+    bL.xc = bL.xt + nu;
+    bL.gc = bL.xc + nu;
+    dl = bL.gc + nu;  // box_lds_doubles(nu) further on
+  }
   int* trn = (int*)(dl + (pref ? D : 0));
   double* T4 = A;
   double* Vn = V;
@@ -703,6 +851,14 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       }
     }
     for (int a = tid; a < nu; a += BW_THREADS) r[a] = dn(2 * nv * nv + nv * nu + nx + a);
+    if constexpr (BOX) {
+      // the bounds on this step's feed-forward: lo - u*, hi - u*
+      for (int a = tid; a < nu; a += BW_THREADS) {
+        const double us = tr.ctrl[pc * nu + a];
+        bL.bl[a] = bx.lo[a] - us;
+        bL.bh[a] = bx.hi[a] - us;
+      }
+    }
     __syncthreads();
     for (int i = tid; i < nx; i += BW_THREADS) Vs[i + i * LX] += mu;
     __syncthreads();
@@ -728,6 +884,7 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       double sm = 0;
       for (int kk = 0; kk < nx; kk++) sm += T1[a + kk * nu] * B[kk + b * LX];
       Mm[e] = -2 * sm - 2 * (r[a] * r[b]);
+      if constexpr (BOX) bL.Mo[e] = Mm[e];
     }
     ILP3_BEGIN(nu * nx)
       double s0 = 0, s1 = 0, s2 = 0;
@@ -774,6 +931,55 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     }
     __syncthreads();
     BSTAMP(3);
+    if constexpr (BOX) {
+      // fast path: the unconstrained k inside the box (a NaN counts as inside
+      // and propagates as in the exact engine) -- K, k stay the exact engine's
+      int inside = 1;
+      for (int a = 0; a < nu; a++) {
+        const double ka = kl[a];
+        inside &= (!(ka < bL.bl[a]) && !(ka > bL.bh[a])) ? 1 : 0;
+      }
+      unsigned cmask = 0, cinfo = 0;
+      if (box_uni(!inside)) {
+        const unsigned full = nu >= 32 ? ~0u : ((1u << nu) - 1u);
+        const int it = box_solve(nu, bL, Mm, col, kl, trn, y, tid, &cmask);  // y is free until stage 5
+        if (box_uni(it >= 0)) {
+          // K: zero rows for the clamped controls, Mm_ff K_f = (2 T3)_f for the
+          // free ones (the final set's factor, its clamped rows isolated)
+          cinfo = (unsigned)it;
+          if (cmask != full) {
+            for (int j = tid; j < nx; j += BW_THREADS) {
+              double* xk = Kl + j * nu;
+              for (int a = 0; a < nu; a++) xk[a] = ((cmask >> a) & 1u) ? 0.0 : 2 * T3[a + j * nu];
+              ldlt_solve(nu, Mm, trn, xk);
+              for (int a = 0; a < nu; a++)
+                if ((cmask >> a) & 1u) xk[a] = 0.0;
+            }
+          } else {
+            for (int e = tid; e < nu * nx; e += BW_THREADS) Kl[e] = 0.0;
+          }
+          if (tid < nu) kl[tid] = bL.x[tid];
+        } else {
+          // fallback: the clipped unconstrained k, zero gain rows where it clipped
+          cmask = 0;
+          for (int a = 0; a < nu; a++) {
+            const double ka = kl[a];
+            if (ka < bL.bl[a] || ka > bL.bh[a]) cmask |= 1u << a;
+          }
+          cmask = (unsigned)box_uni((int)cmask);
+          cinfo = 0x80000000u;
+          wave_sync();
+          for (int e = tid; e < nu * nx; e += BW_THREADS)
+            if ((cmask >> (e % nu)) & 1u) Kl[e] = 0.0;
+          if (tid < nu) kl[tid] = box_clip(kl[tid], bL.bl[tid], bL.bh[tid]);
+        }
+        __syncthreads();
+      }
+      if (tid == 0) {
+        bx.mask[pc] = cmask;
+        bx.info[pc] = cinfo;
+      }
+    }
     // stage 5: ABK = A + B K ; T6 = K'R ; y = Bk + c ; kR = k'R
     for (int e = tid; e < nx * nx; e += BW_THREADS) {
       int i = e % nx, j = e / nx;

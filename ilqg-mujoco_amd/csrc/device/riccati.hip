@@ -65,6 +65,31 @@ __global__ __launch_bounds__(BW_THREADS) void k_backward(DevModel m, int nq, int
                           nullptr, 0u, nullptr, fl);
 }
 
+// the boxed recursion (BoxDev, kernels.h): backward_seed's LDS formulation with
+// each step's feed-forward confined to the control limits; never streamed
+template <int NV_, int NU_>
+__global__ __launch_bounds__(BW_THREADS) void k_backward_box(DevModel m, int nq, int nv_rt, int nu_rt, int P,
+                                                             double dt, double mu, const double* deriv, int Ds,
+                                                             TrajDev tr, double* Kg, double* kg, double* Vg, double* vg,
+                                                             RicFlags fl, BoxDev bx) {
+  extern __shared__ double sh[];
+  backward_seed<NV_, NU_, true>(m, nq, nv_rt, nu_rt, P, dt, mu, deriv, Ds, tr, Kg, kg, Vg, vg, blockIdx.x, threadIdx.x,
+                                sh, nullptr, 0u, nullptr, fl, bx);
+}
+
+template <int NV, int NU>
+hipError_t launch_box_t(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr, double* K,
+                        double* k, double* V, double* v, RicFlags fl, BoxDev bx, size_t lds, hipStream_t st) {
+  if (lds > 65536) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_backward_box<NV, NU>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((k_backward_box<NV, NU>), dim3(S), dim3(BW_THREADS), lds, st, m, m.nq, m.nv, m.nu, P,
+                     m.opt_timestep, mu, deriv, Ds, tr, K, k, V, v, fl, bx);
+  return hipGetLastError();
+}
+
 template <int NV, int NU>
 void launch_t(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr, double* K,
               double* k, double* V, double* v, RicFlags fl, size_t lds, hipStream_t st) {
@@ -143,6 +168,21 @@ hipError_t launch_backward(const DevModel& m, int S, int P, double mu, const dou
   else if (m.nv == 2 && m.nu == 1) launch_t<2, 1>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, lds, st);
   else launch_t<0, 0>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, lds, st);
   return hipGetLastError();
+}
+
+// k_backward's workspace, Mm's copy and the box solve's nu-vectors
+size_t backward_box_lds_bytes(int nv, int nu) {
+  return backward_lds_bytes(nv, nu) + box_lds_doubles((size_t)nu) * sizeof(double);
+}
+
+hipError_t launch_backward_box(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
+                               double* K, double* k, double* V, double* v, RicFlags fl, BoxDev bx, hipStream_t st) {
+  if (m.nu > 32 || !bx.lo || !bx.hi || !bx.mask || !bx.info) return hipErrorInvalidValue;  // the mask's 32 bits
+  const size_t lds = backward_box_lds_bytes(m.nv, m.nu);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (m.nv == 6 && m.nu == 3) return launch_box_t<6, 3>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
+  if (m.nv == 2 && m.nu == 1) return launch_box_t<2, 1>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
+  return launch_box_t<0, 0>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
 }
 
 // ilqg_selftest_div: the split division (dsmall.h) against nothing but the

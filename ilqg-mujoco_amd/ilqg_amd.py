@@ -69,6 +69,7 @@ EXPORTS = [
     "ilqg_fd_sweep_range", "ilqg_solver_device_deriv", "ilqg_solver_set_groups", "ilqg_solver_get_groups",
     "ilqg_solver_join_stream", "ilqg_source_sha", "ilqg_forward_sharded", "ilqg_point_owners",
     "ilqg_solver_point_owners",
+    "ilqg_model_ctrlrange", "ilqg_solver_set_ctrl_limits", "ilqg_solver_get_ctrl_limits", "ilqg_solver_get_clamped",
 ]
 KERNELS = ("rollout", "select", "fd_centre", "fd_cols", "backward", "fd_backward")
 
@@ -271,6 +272,13 @@ class Model:
         v = ctypes.c_int()
         _check(lib().ilqg_model_static_id(self._h, ctypes.byref(v)))
         return v.value
+
+    def ctrlrange(self):
+        """(lo, hi), nu each: the actuators' ctrlrange where ctrllimited, else
+        -inf / +inf (ilqg_model_ctrlrange)"""
+        lo, hi = np.zeros(self.nu), np.zeros(self.nu)
+        _check(lib().ilqg_model_ctrlrange(self._h, _ptr(lo), _ptr(hi)), "ilqg_model_ctrlrange")
+        return lo, hi
 
     def reset_state(self, n=1):
         """mj_resetData: qpos0, zero velocity/warmstart/ctrl/time."""
@@ -494,6 +502,48 @@ class ILQR:
         """Levenberg-Marquardt constant (ILQR::mu, inc/ilqr.h:65,166) for the
         backward passes enqueued from now on: ilqg_solver_set_mu"""
         _check(lib().ilqg_solver_set_mu(self._h, ctypes.c_double(mu)), "set_mu")
+
+    def set_ctrl_limits(self, lo=None, hi=None):
+        """control limits (ilqg_solver_set_ctrl_limits; the reference has none):
+        the backward pass solves each step's feed-forward inside
+        [lo - u*, hi - u*] (clamped controls get zero gain rows) and the rollout
+        clamps the control law to [lo, hi].  lo, hi: nu values each (a scalar is
+        repeated), +-inf = unbounded; lo="model" takes the model's ctrlrange;
+        (None, None) switches the feature off again."""
+        if isinstance(lo, str):
+            if lo != "model" or hi is not None:
+                raise IlqgError('set_ctrl_limits: the only string is lo="model", without hi')
+            lo, hi = self.model.ctrlrange()
+        nu = self.model.nu
+
+        def arr(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=np.float64)
+            x = np.full(nu, float(x)) if x.ndim == 0 else np.ascontiguousarray(x.ravel())
+            if x.size != nu:
+                raise IlqgError(f"control limits must hold {nu} values")
+            return x
+        lo, hi = arr(lo), arr(hi)
+        _check(lib().ilqg_solver_set_ctrl_limits(self._h, _ptr(lo), _ptr(hi)), "set_ctrl_limits")
+
+    def ctrl_limits(self):
+        """(lo, hi) in force, or None while control limits are off (ilqg_solver_get_ctrl_limits)"""
+        lo, hi = np.zeros(self.model.nu), np.zeros(self.model.nu)
+        on = ctypes.c_int(0)
+        _check(lib().ilqg_solver_get_ctrl_limits(self._h, _ptr(lo), _ptr(hi), ctypes.byref(on)), "get_ctrl_limits")
+        return (lo, hi) if on.value else None
+
+    def clamped(self):
+        """(mask, info), uint32 (S, P) each, of the last backward pass
+        (ilqg_solver_get_clamped): bit a of mask = control a clamped in that
+        step's solution; info = the step's QP iterations, bit 31 = fallback.
+        Zeros at point 0 and after a pass without limits."""
+        mask = np.zeros((self.S, self.P), dtype=np.uint32)
+        info = np.zeros((self.S, self.P), dtype=np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        _check(lib().ilqg_solver_get_clamped(self._h, mask.ctypes.data_as(up), info.ctypes.data_as(up)), "get_clamped")
+        return mask, info
 
     def set_groups(self, ngroups: int):
         """seed groups (ilqg_solver_set_groups): iterate() software-pipelines

@@ -81,6 +81,11 @@ void ilqg_model_free(ilqg_model* m);
 int ilqg_model_sizes(const ilqg_model* m, int* sizes);
 int ilqg_model_timestep(const ilqg_model* m, double* dt);
 int ilqg_model_qpos0(const ilqg_model* m, double* qpos0);
+/* the actuators' control ranges (mjModel.actuator_ctrlrange, which mj_fwdActuation
+   clips to where actuator_ctrllimited): lo[a], hi[a] (nu doubles each) where
+   actuator a is ctrllimited, else -inf / +inf.  The reference never reads them
+   on the optimiser's side (no counterpart call); see ilqg_solver_set_ctrl_limits. */
+int ilqg_model_ctrlrange(const ilqg_model* m, double* lo, double* hi);
 /* compiled-model record (include/ilqg_model_blob.h); needed = bytes required */
 int ilqg_model_blob(const ilqg_model* m, void* buf, size_t cap, size_t* needed);
 /* specialisation key: the integer data (sizes, topology, static collision
@@ -213,6 +218,41 @@ int ilqg_solver_set_value(ilqg_solver* s, const double* V, const double* v);
    by every backward step at inc/ilqr.h:166): used by every backward pass
    enqueued after the call (opts.mu at creation until then).  NaN is refused. */
 int ilqg_solver_set_mu(ilqg_solver* s, double mu);
+/* Control limits: a box-constrained backward pass and a clamped rollout.  The
+   reference has no counterpart (inc/ilqr.h solves the unconstrained
+   Quu k = ..., stores u unclamped and leaves any clipping to the physics); an
+   extension in the spirit of ILQG_LAYOUT_CORRECTED, off by default.
+   lo, hi: nu doubles each, lo <= hi, +-inf = unbounded on that side.  Both
+   NULL switches the feature off again (ilqg_iterate is then the solver's as
+   created, the fused sweep included).  ILQG_ERR_ARG: lo[a] > hi[a], any NaN,
+   exactly one of lo, hi NULL.  Synchronises like ilqg_solver_set_mu and applies
+   to every launch enqueued after it.  With limits on:
+   - ilqg_backward (and the backward pass ilqg_iterate ends in) solves, per
+     step, min 1/2 k'Quu k + Qu'k over lo - u* <= k <= hi - u* by projected
+     Newton (Tassa, Mansard & Todorov 2014); clamped controls get zero rows of
+     K, free ones the free block's gains; a step whose unconstrained k lies
+     inside the box is the exact engine's, bit for bit.  A free block that is
+     not definite (mu = 0 rank-one cases) or an exhausted iteration cap takes
+     the fallback: k = clip(unconstrained k), zero K rows where it clipped.
+   - ilqg_forward stores and charges u = clip(K(x - x*) + alpha k + u*); the
+     constructor's passive rollout and the FD sweep are untouched.
+   - ilqg_iterate runs rollout, selection, sweep, ilqg_backward unfused.
+   ILQG_ERR_UNSUPPORTED, from whichever call comes second: with the MFMA
+   engine, with seed groups > 1, and from the forward calls when ILQG_DUAL=0
+   selects a rollout kernel without a clamped variant.  fp32 FD, both layouts,
+   set_value, set_mu, set_deriv and ilqg_forward_sharded compose with limits.
+   Limits wider than a ctrllimited model's own ctrlrange leave the physics
+   clipping inside them: pass ilqg_model_ctrlrange's arrays. */
+int ilqg_solver_set_ctrl_limits(ilqg_solver* s, const double* lo, const double* hi);
+/* the limits in force (-inf / +inf when off) and whether they are on; any
+   pointer may be NULL.  No counterpart in the reference. */
+int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* enabled);
+/* after a backward pass with limits, per (seed, point) (nseed x (N+1) words
+   each, either may be NULL): mask, bit a = control a clamped in that step's
+   solution; info, the step's QP iterations, bit 31 = the fallback was taken.
+   Point 0 (no step) and every entry after a pass without limits read 0.
+   Synchronises.  No counterpart in the reference. */
+int ilqg_solver_get_clamped(ilqg_solver* s, unsigned* mask, unsigned* info);
 /* Riccati recursion (inc/ilqr.h:133-176) engine.  EXACT (default): the
    oracle's loops, bit-identical K, k, V, v (streamed behind the FD sweep on
    cooperative models).  MFMA: every matrix product (B'V, Quu = -2B'VB - 2R,
