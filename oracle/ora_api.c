@@ -27,6 +27,7 @@ mjtNum* ora_d_field(mjData* d, int which) {
     case 12: return d->xpos;
     case 13: return d->efc_D;
     case 14: return d->efc_aref;
+    case 15: return d->efc_pos;
     default: return 0;
   }
 }
@@ -38,6 +39,16 @@ int ora_d_int(const mjData* d, int which) {
     case 3: return d->maxuse_stack;
     default: return -1;
   }
+}
+/* contact i: out = dist, pos[3], normal[3] (frame row 0); iout = geom1, geom2, dim, efc_address */
+int ora_contact(const mjData* d, int i, double* out, int* iout) {
+  const mjContact* c;
+  if (i < 0 || i >= d->ncon) return -1;
+  c = d->contact + i;
+  out[0] = (double)c->dist;
+  for (int k = 0; k < 3; k++) { out[1 + k] = (double)c->pos[k]; out[4 + k] = (double)c->frame[k]; }
+  iout[0] = c->geom1; iout[1] = c->geom2; iout[2] = c->dim; iout[3] = c->efc_address;
+  return 0;
 }
 void ora_set_solver(mjModel* m, int iterations, double tolerance) {
   m->opt.iterations = iterations;

@@ -64,6 +64,8 @@ class Lib:
         L.ora_d_int.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.ora_model_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), _dp]
         L.ora_set_solver.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        if hasattr(L, "ora_contact"):  # a reference build from before the accessor keeps loading
+            L.ora_contact.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_int)]
         L.ora_get_solver.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), _dp]
         L.ora_cpMjData.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ora_calcMJDerivatives.argtypes = [ctypes.c_void_p, ctypes.c_void_p, _dp, ctypes.c_void_p]
@@ -184,6 +186,26 @@ class OData:
 
     def solver_iter(self):
         return self.lib.L.ora_d_int(self.d, 2)
+
+    def contacts(self):
+        """every contact: dict(dist, pos, normal, geom1, geom2, dim, efc_address)"""
+        out = []
+        for i in range(self.ncon()):
+            f, k = np.zeros(7), (ctypes.c_int * 4)()
+            if self.lib.L.ora_contact(self.d, i, f.ctypes.data_as(_dp), k):
+                raise IndexError(i)
+            out.append(dict(dist=f[0], pos=f[1:4].copy(), normal=f[4:7].copy(), geom1=k[0], geom2=k[1], dim=k[2],
+                            efc_address=k[3]))
+        return out
+
+    def efc(self, name):
+        """efc_J (nefc, nv), efc_D, efc_aref or efc_pos (nefc) of the last forward"""
+        idx = {"efc_J": 11, "efc_D": 13, "efc_aref": 14, "efc_pos": 15}[name]
+        ne, nv = self.nefc(), self.model.nv
+        p = self.lib.L.ora_d_field(self.d, idx)
+        if ne == 0:
+            return np.zeros((0, nv) if name == "efc_J" else 0)
+        return np.ctypeslib.as_array(p, shape=(ne, nv) if name == "efc_J" else (ne,)).copy()
 
     def step(self, n=1):
         for _ in range(n):

@@ -127,6 +127,7 @@ class Compiled:
 
 
 def compile_mjcf(path):
+    """path: a file name or an open file (io.StringIO for a model written in a test)"""
     root = ET.parse(path).getroot()
     comp = root.find("compiler")
     cattr = comp.attrib if comp is not None else {}
@@ -141,6 +142,7 @@ def compile_mjcf(path):
     opt = root.find("option")
     oa = opt.attrib if opt is not None else {}
     M = Compiled()
+    M.angle_unit = ang  # radians per unit of a hinge's ref / springref / range attribute
     M.timestep = strtod_list(oa.get("timestep", "0.002"))[0]
     M.gravity = (strtod_list(oa.get("gravity", "0 0 -9.81")) + [0, 0, -9.81])[:3]
     M.integrator = {"Euler": 0, "RK4": 1}[oa.get("integrator", "Euler")]
