@@ -322,6 +322,14 @@ struct ilqg_solver {
   bool limits = false, cl_valid = false;
   std::vector<double> host_lim;
   DevBuf ulim, cl_mask, cl_info;
+  // cost schedule (ilqg_solver_set_cost_schedule): one packed cost row per
+  // trajectory point, [P][csz], shared by every seed; sched[sched_cur] is the
+  // table in force and the other buffer the target of the next shift (a shift
+  // in place would overlap itself).  host_cost: the creation cost, packed.
+  bool sched_on = false;
+  int sched_cur = 0, csz = 0;
+  DevBuf sched[2];
+  std::vector<double> host_cost;
   // the fused sweep streams the bit-exact, unboxed recursion behind the fp64 sweep
   void choose_fused();
   bool timing = false;
@@ -357,8 +365,17 @@ struct ilqg_solver {
   TrajDev tview(DevBuf* b) const {
     return TrajDev{b[0].as<double>(), b[1].as<double>(), b[2].as<double>(), b[3].as<double>(), b[4].as<double>()};
   }
-  CostDev cview() const {
-    const double* c = cost.as<double>();
+  // the creation cost (the constructor's passive rollout)
+  CostDev cview0() const { return cat(cost.as<double>()); }
+  // the cost the launches charge: the creation cost, or row p0 of the schedule
+  // (a launch whose point 0 is the trajectory's point p0) with cstride() doubles
+  // from one point's row to the next (0 without a schedule)
+  CostDev cview(int p0 = 0) const {
+    if (!sched_on) return cview0();
+    return cat(sched[sched_cur].as<double>() + (size_t)p0 * csz);
+  }
+  int cstride() const { return sched_on ? csz : 0; }
+  CostDev cat(const double* c) const {
     const int nq = model->host.nq, nv = model->host.nv, nu = model->host.nu;
     return CostDev{c, c + nq, c + 2 * nq, c + 3 * nq, c + 3 * nq + nv, c + 3 * nq + 2 * nv,
                    c + 3 * nq + 3 * nv, c + 3 * nq + 3 * nv + nu, c + 3 * nq + 3 * nv + 2 * nu};
@@ -782,6 +799,8 @@ int ilqg_solver_create(const ilqg_model* mc, const ilqg_solver_opts* o, const il
   ALLOC(s->alphas, A * 8);
   std::vector<double> cp = pack_cost(h, cost);
   ALLOC(s->cost, cp.size() * 8);
+  s->host_cost = cp;
+  s->csz = (int)cp.size();
   e = hipMemcpy(s->alphas.p, s->host_alphas.data(), A * 8, hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail_free(e, "alphas");
   e = hipMemcpy(s->cost.p, cp.data(), cp.size() * 8, hipMemcpyHostToDevice);
@@ -826,7 +845,7 @@ int ilqg_solver_init(ilqg_solver* s, const double* time, const double* qpos, con
   TrajDev nom = s->tview(s->traj), di = s->tview(s->dinit);
   HIPCHK(launch_rollout_coop(m->dm, m->Lc, m->C, m->X, s->S, 1, s->P, nom, nom, 0, s->K.as<double>(),
                              s->k.as<double>(), nullptr, di, s->qfrc_applied.as<double>(),
-                             s->xfrc_applied.as<double>(), 1, s->cview(), nullptr, s->stream));
+                             s->xfrc_applied.as<double>(), 1, s->cview0(), nullptr, s->stream));
   HIPCHK(s->sync_all());
   // setDInit(dmain) as the MPC driver does before iterating (src/inverted_pendulum/inverted_pendulum.cpp:21)
   s->initialized = true;
@@ -926,10 +945,13 @@ static TrajDev toff(TrajDev t, size_t pts, const HostModel& h) {
   return TrajDev{t.time + pts, t.qpos + pts * h.nq, t.qvel + pts * h.nv, t.warm + pts * h.nv, t.ctrl + pts * h.nu};
 }
 
-// with control limits the rollout must be a kernel that has a clamped variant
+// with control limits the rollout must be a kernel that has a clamped variant,
+// with a cost schedule one that has a scheduled variant
 static int limits_rollout_check(const ilqg_solver* s) {
   if (s->limits && !rollout_clamp_supported())
     return fail(ILQG_ERR_UNSUPPORTED, "control limits: the rollout kernel selected by ILQG_DUAL=0 has no clamped variant");
+  if (s->sched_on && !rollout_sched_supported())
+    return fail(ILQG_ERR_UNSUPPORTED, "cost schedule: the rollout kernel selected by ILQG_DUAL=0 has no scheduled variant");
   return ILQG_OK;
 }
 
@@ -977,7 +999,7 @@ static hipError_t rollout_launch(ilqg_solver* s, const SeedRange& r, RollChunk c
   if (s->limits) ch.ulim = s->ulim.as<double>();
   return s->timed(0, [&] {
     return launch_rollout_coop(m->dm, m->Lc, m->C, m->X, r.ns, s->A, s->P, nom, outv, multi ? 1 : 0, K, k,
-                               s->alphas.as<double>(), di, qa, xf, 0, s->cview(), cc, r.st, ch);
+                               s->alphas.as<double>(), di, qa, xf, 0, s->cview(), cc, r.st, ch, s->cstride());
   }, r.st);
 }
 
@@ -1254,7 +1276,7 @@ static hipError_t fused_launch(ilqg_solver* s, const SeedRange& r, int mode, boo
     if (e != hipSuccess) return e;
     a.order = s->plan_order.as<unsigned>();
   }
-  return launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, r.st);
+  return launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, r.st, s->cstride());
 }
 
 int ilqg_fd_sweep(ilqg_solver* s) {
@@ -1271,19 +1293,20 @@ int ilqg_fd_sweep(ilqg_solver* s) {
     HIPCHK(s->timed(3, [&] {
       return launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
                                  s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                                 s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, ILQG_FD32_EPS, s->stream);
+                                 s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, ILQG_FD32_EPS, s->stream,
+                                 s->cstride());
     }));
     return ILQG_OK;
   }
   HIPCHK(s->timed(2, [&] {
     return launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
                                  s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                                 s->cost_c.as<double>(), s->stream);
+                                 s->cost_c.as<double>(), s->stream, s->cstride());
   }));
   HIPCHK(s->timed(3, [&] {
     return launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
                                s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                               s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, s->stream);
+                               s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, s->stream, s->cstride());
   }));
   return ILQG_OK;
 }
@@ -1296,7 +1319,9 @@ int ilqg_fd_sweep(ilqg_solver* s) {
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st) {
   const ilqg_model* m = s->model;
   const HostModel& h = m->host;
-  constexpr int kOneSeed = 1 << 30;  // the kernels' seed index pt / P is 0 for every point of the range
+  // the kernels' seed index pt / P is 0 for every point of the range, and their
+  // point index pt % P counts from p0: the cost schedule is passed from row p0 on
+  constexpr int kOneSeed = 1 << 30;
   for (int sd = 0; sd < s->S; sd++) {
     const size_t pt0 = (size_t)sd * s->P + p0;
     const TrajDev nom = toff(s->tview(s->traj), pt0, h);
@@ -1307,13 +1332,14 @@ static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st
     double* dv = s->deriv.as<double>() + pt0 * s->Dp;
     hipError_t e;
     if (s->fdprec == ILQG_FD_F32) {
-      e = launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(), wc, cc, dv, s->Dp,
-                              ILQG_FD32_EPS, st);
+      e = launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, dv, s->Dp,
+                              ILQG_FD32_EPS, st, s->cstride());
     } else {
-      e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(), wc, cc, st);
+      e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, st,
+                                s->cstride());
       if (e == hipSuccess)
-        e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(), wc, cc, dv, s->Dp,
-                                st);
+        e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, dv, s->Dp,
+                                st, s->cstride());
     }
     if (e != hipSuccess) return e;
   }
@@ -1539,6 +1565,62 @@ int ilqg_solver_set_ctrl_limits(ilqg_solver* s, const double* lo, const double* 
   HIPCHK(hipMemcpy(s->ulim.p, s->host_lim.data(), 2 * nu * 8, hipMemcpyHostToDevice));
   s->limits = true;
   s->fused = false;  // rollout, select, sweep, then the boxed ilqg_backward
+  return ILQG_OK;
+}
+
+static bool all_finite(const double* a, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+
+int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  const size_t n = (size_t)s->P * s->csz;
+  if (!rows) {  // off: the solver as it was created
+    HIPCHK(s->sync_all());
+    s->sched_on = false;
+    return ILQG_OK;
+  }
+  if (!all_finite(rows, n)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
+  HIPCHK(s->sync_all());  // launches already enqueued keep the rows they were given
+  for (auto& b : s->sched)
+    if (!b.p) HIPCHK(b.alloc(n * 8));
+  HIPCHK(hipMemcpy(s->sched[s->sched_cur].p, rows, n * 8, hipMemcpyHostToDevice));
+  s->sched_on = true;
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (enabled) *enabled = s->sched_on ? 1 : 0;
+  if (!rows) return ILQG_OK;
+  if (s->sched_on) {
+    HIPCHK(s->sync_all());
+    HIPCHK(hipMemcpy(rows, s->sched[s->sched_cur].p, (size_t)s->P * s->csz * 8, hipMemcpyDeviceToHost));
+  } else {
+    for (int p = 0; p < s->P; p++) std::copy(s->host_cost.begin(), s->host_cost.end(), rows + (size_t)p * s->csz);
+  }
+  return ILQG_OK;
+}
+
+int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (!s->sched_on) return fail(ILQG_ERR_ARG, "cost schedule: shift without a schedule (set one first)");
+  if (n < 1 || n > s->P) return fail(ILQG_ERR_ARG, "cost schedule: shift must be in 1 .. horizon + 1");
+  if (!new_rows) return fail(ILQG_ERR_ARG, "cost schedule: null new_rows");
+  const size_t C = s->csz;
+  if (!all_finite(new_rows, (size_t)n * C)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
+  HIPCHK(s->sync_all());
+  // into the second buffer, then swap: rows n .. P-1 from rows 0 .. P-1-n, the new rows in front
+  double* src = s->sched[s->sched_cur].as<double>();
+  double* dst = s->sched[1 - s->sched_cur].as<double>();
+  // (on the solver's stream and waited for: its streams do not order with the null stream)
+  if (n < s->P)
+    HIPCHK(hipMemcpyAsync(dst + (size_t)n * C, src, (size_t)(s->P - n) * C * 8, hipMemcpyDeviceToDevice, s->stream));
+  HIPCHK(hipMemcpyAsync(dst, new_rows, (size_t)n * C * 8, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  s->sched_cur = 1 - s->sched_cur;
   return ILQG_OK;
 }
 

@@ -38,6 +38,16 @@ struct RollChunk {
 struct CostDev {
   const double *wq, *tq, *lq, *wv, *tv, *lv, *wu, *tu, *lu;
 };
+// Cost schedule (ilqg_solver_set_cost_schedule): the descriptor's arrays are
+// row 0 of a [point][3 (nq + nv + nu)] table, packed wq tq lq wv tv lv wu tu lu,
+// and point p is charged with the row `stride` doubles further on per point.
+// The launches below take the stride as `cstride` (0 = one stationary cost:
+// the kernels they always launched); != 0 launches the *_sch instances, which
+// carry it as an extra kernel argument.
+__host__ __device__ inline CostDev cost_at(const CostDev& c, int p, int stride) {
+  const size_t o = (size_t)p * (size_t)stride;
+  return CostDev{c.wq + o, c.tq + o, c.lq + o, c.wv + o, c.tv + o, c.lv + o, c.wu + o, c.tu + o, c.lu + o};
+}
 
 // How the Riccati recursion reads an FD record (ilqg_solver_set_layout).
 // The record is always the reference's (row-major by output, mjderivative.cpp:
@@ -157,28 +167,31 @@ size_t coop_lds_bytes(const WsLayout& L, const coop::CoopLayout& C);
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                  const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
                                  const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                                 hipStream_t st);
+                                 hipStream_t st, int cstride = 0);
 hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
                                const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c,
-                               double* deriv, int Ds, hipStream_t st);
+                               double* deriv, int Ds, hipStream_t st, int cstride = 0);
 // fp32 FD sweep (kernels_fd32.hip; BASELINE.json configs[4]): centre + column
 // kernels on the fp32 physics, fp64 records; eps is the FD step (1e-3)
 size_t coop_lds_bytes_f32(const WsLayout& L, const coop::CoopLayout& C);
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
                                const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                               double* deriv, int Ds, double eps, hipStream_t st);
+                               double* deriv, int Ds, double eps, hipStream_t st, int cstride = 0);
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                                const coop::CoopAux& X, const FdFused& a, hipStream_t st);
+                                const coop::CoopAux& X, const FdFused& a, hipStream_t st, int cstride = 0);
 hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, int S, int A, int P, TrajDev nominal, TrajDev out,
                                int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit,
                                const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost,
-                               double* cost_cand, hipStream_t st, RollChunk ch = RollChunk{});
+                               double* cost_cand, hipStream_t st, RollChunk ch = RollChunk{}, int cstride = 0);
 // whether the rollout kernel this process selects (ILQG_DUAL) has a clamped
 // variant (RollChunk.ulim): launch_rollout_coop refuses limits otherwise
 bool rollout_clamp_supported();
+// the same for a cost schedule (cstride != 0): the scheduled variants re-stage
+// the LDS cost copy per point
+bool rollout_sched_supported();
 // n independent states, one wavefront each: nstep mj_step (in place)
 hipError_t launch_step_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
                             TrajDev stt, int n, int nstep, const double* qfrc_applied, const double* xfrc_applied,

@@ -12,10 +12,15 @@
 namespace ilqg {
 namespace {
 
+// sched (the *_sch kernels, launched while a cost schedule is set,
+// kernels.h cost_at): the point's costs are taken from its own row of the
+// schedule, `cstride` doubles per point past the descriptor's arrays
 __device__ inline void fd_centre_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c) {
+                                TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
+                                auto sched, int cstride) {
   STAMP_INIT();
   const int pt = blockIdx.x;
+  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt % P, cstride);
   load_state(m, L, T, tr, pt, pt / P, qfrc_applied, xfrc_applied);
   forward_skip(m, L, C, X, T, STAGE_NONE, FD_NITER, 0.0);
   for (int rep = 1; rep < FD_NWARMUP; rep++) forward_skip(m, L, C, X, T, STAGE_VEL, FD_NITER, 0.0);
@@ -31,7 +36,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevMod
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::false_type{}, 0);
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
@@ -43,16 +48,18 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel 
   Team T = make_team(L, C);
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::false_type{}, 0);
 }
 
 __device__ inline void fd_cols_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds) {
+                                TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds,
+                                auto sched, int cstride) {
   STAMP_INIT();
   const int nv = m.nv, nu = m.nu;
   const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   const int ncol = nctrl + 2 * nv;
   const int pt = blockIdx.x / ncol, col = blockIdx.x % ncol;
+  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt % P, cstride);
   double* dr = deriv + (size_t)pt * Ds;  // record stride Ds >= D
   const double* wc = warm_c + (size_t)pt * nv;
   const double costCenter = cost_c[pt];
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::false_type{}, 0);
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
@@ -147,7 +154,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg
   Team T = make_team(L, C);
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::false_type{}, 0);
 }
 
 // ---- fused FD sweep with the backward pass streamed behind it ------------
@@ -259,8 +266,9 @@ __device__ __forceinline__ int snap_dst(int e, const int (&o)[SNAP_NR], const in
   return d;
 }
 
+// (sched, cstride: as fd_centre_body)
 __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                     const FdFused& a, unsigned u) {
+                                     const FdFused& a, unsigned u, auto sched, int cstride) {
   // late tickets first in the SIMD's issue arbitration: they set the launch's tail
   if (u >= a.prio2) __builtin_amdgcn_s_setprio(2);
   else if (u >= a.prio1) __builtin_amdgcn_s_setprio(1);
@@ -290,6 +298,13 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
   const int ntm = a.nut + 2 * nv;
   fd_decode(a, ntm, u, role, s, p, idx, half);
   const int pt = s * a.P + p;
+  // the point's cost: a.cost, or (sched) its row of the schedule
+  [[maybe_unused]] CostDev prow;
+  const CostDev* pc = &a.cost;
+  if constexpr (decltype(sched)::value) {
+    prow = cost_at(a.cost, p, cstride);
+    pc = &prow;
+  }
   double* dr = a.deriv + (size_t)pt * a.Dp;
   double* cwp = a.cw + (size_t)pt * a.WCp;
   unsigned* cflag = a.sync + 4 + pt;
@@ -395,7 +410,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
     forward_skip(m, L, C, X, T, STAGE_VEL, FD_NITER, 0.0);
     forward_skip(m, L, C, X, T, STAGE_VEL, FD_NITER, 0.0);
     wc = tid < nv ? warm[tid] : 0.0;
-    costCenter = step_cost(m, a.cost, qpos, qvel, ctrl);
+    costCenter = step_cost(m, *pc, qpos, qvel, ctrl);
     if (tid < nv) st_sc1(cwp + tid, wc);
     if (tid == 0) st_sc1(cwp + nv, costCenter);
     drain_stores();
@@ -416,7 +431,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
       TSYNC();
       if (tid == 0) {
         ctrl[i] = u0 + sg;
-        if (!half) st_sc1(dr + G + 2 * nv + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+        if (!half) st_sc1(dr + G + 2 * nv + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
       }
       set_warm();
       forward_acc(m, L, C, X, T, FD_NITER, 0.0);
@@ -427,7 +442,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
       if (tid == 0) qvel[i] = v0 + sg;
       forward_posvel(m, L, C, X, T, snap ? STAGE_POS : STAGE_NONE);
       get_centre();
-      if (tid == 0 && !half) st_sc1(dr + G + nv + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+      if (tid == 0 && !half) st_sc1(dr + G + nv + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
       set_warm();
       forward_acc(m, L, C, X, T, FD_NITER, 0.0);
     } else {
@@ -453,7 +468,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
       }
       forward_posvel(m, L, C, X, T, STAGE_NONE);
       get_centre();
-      if (tid == 0 && !half) st_sc1(dr + G + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+      if (tid == 0 && !half) st_sc1(dr + G + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
       set_warm();
       forward_acc(m, L, C, X, T, FD_NITER, 0.0);
     }
@@ -489,7 +504,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
     TSYNC();
     if (tid == 0) {
       ctrl[i] = u0 + FD_EPS;
-      st_sc1(dr + G + 2 * nv + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+      st_sc1(dr + G + 2 * nv + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
     }
     set_warm();
     forward_acc(m, L, C, X, T, FD_NITER, 0.0);
@@ -508,7 +523,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
     // its position stage is the centre's (qpos unchanged): from the snapshot
     forward_posvel(m, L, C, X, T, snap ? STAGE_POS : STAGE_NONE);
     get_centre();
-    if (tid == 0) st_sc1(dr + G + nv + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+    if (tid == 0) st_sc1(dr + G + nv + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
     set_warm();
     forward_acc(m, L, C, X, T, FD_NITER, 0.0);
     const double qp = tid < nv ? qacc[tid] : 0.0;
@@ -544,7 +559,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
     perturb(FD_EPS);
     forward_posvel(m, L, C, X, T, STAGE_NONE);
     get_centre();
-    if (tid == 0) st_sc1(dr + G + i, (step_cost(m, a.cost, qpos, qvel, ctrl) - costCenter) / FD_EPS);
+    if (tid == 0) st_sc1(dr + G + i, (step_cost(m, *pc, qpos, qvel, ctrl) - costCenter) / FD_EPS);
     set_warm();
     forward_acc(m, L, C, X, T, FD_NITER, 0.0);
     const double qp = tid < nv ? qacc[tid] : 0.0;
@@ -603,7 +618,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevMode
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::false_type{}, 0);
 }
 
 // compile-time models: the model read from its global image (L1/L2 cached)
@@ -625,7 +640,74 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
   T.ci = T.iw + L.ni;
   SM m;
   m.bind(mg.img, mg);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::false_type{}, 0);
+}
+
+// ---- the cost-schedule instances of the kernels above: the same bodies with
+// the `sched` tag, the row stride as their last argument
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int cstride) {
+  Team T = make_team(L, C);
+  DevModel m;
+  CoopAux X;
+  stage_model(mg, Xg, L, C, T, m, X);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::true_type{}, cstride);
+}
+template <class SM, class SX>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s_sch(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int cstride) {
+  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
+  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
+  static constexpr SX X{};
+  Team T = make_team(L, C);
+  SM m;
+  stage_model_s(mg, L, C, T, m);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::true_type{}, cstride);
+}
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int cstride) {
+  Team T = make_team(L, C);
+  DevModel m;
+  CoopAux X;
+  stage_model(mg, Xg, L, C, T, m, X);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::true_type{}, cstride);
+}
+template <class SM, class SX>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s_sch(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int cstride) {
+  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
+  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
+  static constexpr SX X{};
+  Team T = make_team(L, C);
+  SM m;
+  stage_model_s(mg, L, C, T, m);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::true_type{}, cstride);
+}
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, FdFused a, int cstride) {
+  const unsigned t = take_ticket(a.sync);
+  if (t < (unsigned)a.nB) {
+    fd_backward_role<0, 0>(mg, a, (int)t);
+    return;
+  }
+  Team T = make_team(L, C);
+  DevModel m;
+  CoopAux X;
+  stage_model(mg, Xg, L, C, T, m, X);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::true_type{}, cstride);
+}
+template <class SM, class SX>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g_sch(DevModel mg, FdFused a, int cstride) {
+  const unsigned t = take_ticket(a.sync);
+  if (t < (unsigned)a.nB) {
+    fd_backward_role<SM::nv, SM::nu>(mg, a, (int)t);
+    return;
+  }
+  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
+  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
+  static constexpr SX X{};
+  extern __shared__ double lds[];
+  Team T = make_team(L, C);
+  T.iw = reinterpret_cast<int*>(lds + L.nd + C.nd);  // no image region
+  T.ci = T.iw + L.ni;
+  SM m;
+  m.bind(mg.img, mg);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::true_type{}, cstride);
 }
 
 // ---- the fused sweep's ticket schedule (launch_fd_plan) -----------------
@@ -770,10 +852,30 @@ size_t coop_lds_bytes(const WsLayout& L, const CoopLayout& C) {
 }
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                  TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
-                                 CostDev cost, double* warm_c, double* cost_c, hipStream_t st) {
+                                 CostDev cost, double* warm_c, double* cost_c, hipStream_t st, int cstride) {
   if (npts <= 0) return hipSuccess;
   const size_t lds = coop_lds_bytes(L, C);
   hipError_t e;
+  if (cstride) {
+#define ILQG_CASE(id, SMT, SXT)                                                                                 \
+  case id:                                                                                                      \
+    e = allow_lds(k_fd_centre_s_sch<stat::SMT, stat::SXT>, lds);                                                \
+    if (e != hipSuccess) return e;                                                                              \
+    hipLaunchKernelGGL((k_fd_centre_s_sch<stat::SMT, stat::SXT>), dim3(npts), dim3(TEAM), lds, st, m, tr, P,     \
+                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, cstride);                              \
+    return hipGetLastError();
+    switch (m.static_id) {
+      ILQG_STATIC_MODELS(ILQG_CASE)
+      default:
+        break;
+    }
+#undef ILQG_CASE
+    e = allow_lds(k_fd_centre_coop_sch, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fd_centre_coop_sch, dim3(npts), dim3(TEAM), lds, st, m, L, C, X, tr, P, qfrc_applied,
+                       xfrc_applied, cost, warm_c, cost_c, cstride);
+    return hipGetLastError();
+  }
 #define ILQG_CASE(id, SMT, SXT)                                                                                 \
   case id:                                                                                                      \
     e = allow_lds(k_fd_centre_s<stat::SMT, stat::SXT>, lds);                                                    \
@@ -797,12 +899,32 @@ hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const Coo
 hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
                                CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds,
-                               hipStream_t st) {
+                               hipStream_t st, int cstride) {
   const int nctrl = m.nu < m.nv ? m.nu : m.nv;
   const long blocks = (long)npts * (nctrl + 2 * m.nv);
   if (blocks <= 0) return hipSuccess;
   const size_t lds = coop_lds_bytes(L, C);
   hipError_t e;
+  if (cstride) {
+#define ILQG_CASE(id, SMT, SXT)                                                                                 \
+  case id:                                                                                                      \
+    e = allow_lds(k_fd_cols_s_sch<stat::SMT, stat::SXT>, lds);                                                  \
+    if (e != hipSuccess) return e;                                                                              \
+    hipLaunchKernelGGL((k_fd_cols_s_sch<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds, st, m,  \
+                       tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, cstride);            \
+    return hipGetLastError();
+    switch (m.static_id) {
+      ILQG_STATIC_MODELS(ILQG_CASE)
+      default:
+        break;
+    }
+#undef ILQG_CASE
+    e = allow_lds(k_fd_cols_coop_sch, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fd_cols_coop_sch, dim3((unsigned)blocks), dim3(TEAM), lds, st, m, L, C, X, tr, P,
+                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, cstride);
+    return hipGetLastError();
+  }
 #define ILQG_CASE(id, SMT, SXT)                                                                                 \
   case id:                                                                                                      \
     e = allow_lds(k_fd_cols_s<stat::SMT, stat::SXT>, lds);                                                      \
@@ -824,7 +946,7 @@ hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const CoopL
 }
 
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
-                                const FdFused& a, hipStream_t st) {
+                                const FdFused& a, hipStream_t st, int cstride) {
   const long items = (long)a.S * a.P * (1 + (a.halves ? 2 : 1) * (a.nut + 2 * m.nv));
   const long blocks = items + a.nB;
   if (items <= 0) return hipSuccess;
@@ -833,6 +955,25 @@ hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const Coop
   hipError_t e;
   const size_t lds_g = std::max((size_t)(L.nd + C.nd) * sizeof(double) + (size_t)(L.ni + C.ni) * sizeof(int),
                                 a.nB > 0 ? backward_lds_bytes(m.nv, m.nu) : (size_t)0);
+  if (cstride) {
+#define ILQG_CASE(id, SMT, SXT)                                                                                 \
+  case id:                                                                                                      \
+    e = allow_lds(k_fd_fused_g_sch<stat::SMT, stat::SXT>, lds_g);                                               \
+    if (e != hipSuccess) return e;                                                                              \
+    hipLaunchKernelGGL((k_fd_fused_g_sch<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds_g, st, \
+                       m, a, cstride);                                                                          \
+    return hipGetLastError();
+    switch (m.static_id) {
+      ILQG_STATIC_MODELS(ILQG_CASE)
+      default:
+        break;
+    }
+#undef ILQG_CASE
+    e = allow_lds(k_fd_fused_coop_sch, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fd_fused_coop_sch, dim3((unsigned)blocks), dim3(TEAM), lds, st, m, L, C, X, a, cstride);
+    return hipGetLastError();
+  }
 #define ILQG_CASE(id, SMT, SXT)                                                                                 \
   case id:                                                                                                      \
     e = allow_lds(k_fd_fused_g<stat::SMT, stat::SXT>, lds_g);                                                   \

@@ -90,15 +90,20 @@ __device__ inline void load_state32(const DevModel& m, const WsLayout& L, const 
 
 // MT: DevModel, or DevModelNV<27> for 27-dof models (the humanoid: compile-time
 // sizes in the Newton Cholesky and its substitution, as the rollout's instance)
-template <class MT>
+// SCH: empty, or one int -- the instances launched while a cost schedule is set
+// (kernels.h cost_at), whose extra last argument is the schedule's row stride:
+// the point's costs are taken from its own row.  (A parameter pack and not a
+// second body: the instances without a schedule keep the code they had.)
+template <class MT, class... SCH>
 __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L, coop::CoopLayout C, coop::CoopAux X,
                                                         TrajDev tr, int P, const double* qfrc_applied,
                                                         const double* xfrc_applied, CostDev cost, double* warm_c,
-                                                        double* cost_c) {
+                                                        double* cost_c, SCH... cstride) {
   MT m;
   static_cast<DevModel&>(m) = mg;
   Team T = make_team32(L, C);
   const int pt = blockIdx.x;
+  if constexpr (sizeof...(SCH) > 0) cost = cost_at(cost, pt % P, (cstride, ...));
   load_state32(m, L, T, tr, pt, pt / P, qfrc_applied, xfrc_applied);
   // every physics call inlined (FD32_INL): see k_fd_cols32
   FD32_INL forward_skip(m, L, C, X, T, STAGE_NONE, FD32_NITER, 0.0);
@@ -108,11 +113,12 @@ __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L,
   if (T.tid == 0) cost_c[pt] = step_cost32(m, cost, T.w + L.qpos, T.w + L.qvel, T.w + L.ctrl);
 }
 
-template <class MT>
+template <class MT, class... SCH>
 __global__ __launch_bounds__(TEAM32) void k_fd_cols32(DevModel mg, WsLayout L, coop::CoopLayout C, coop::CoopAux X,
                                                       TrajDev tr, int P, const double* qfrc_applied,
                                                       const double* xfrc_applied, CostDev cost, const double* warm_c,
-                                                      const double* cost_c, double* deriv, int Ds, float eps) {
+                                                      const double* cost_c, double* deriv, int Ds, float eps,
+                                                      SCH... cstride) {
   MT m;
   static_cast<DevModel&>(m) = mg;
   Team T = make_team32(L, C);
@@ -120,6 +126,7 @@ __global__ __launch_bounds__(TEAM32) void k_fd_cols32(DevModel mg, WsLayout L, c
   const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   const int ncol = nctrl + 2 * nv;
   const int pt = blockIdx.x / ncol, col = blockIdx.x % ncol;
+  if constexpr (sizeof...(SCH) > 0) cost = cost_at(cost, pt % P, (cstride, ...));
   double* dr = deriv + (size_t)pt * Ds;
   const double* wc = warm_c + (size_t)pt * nv;
   const float costCenter = (float)cost_c[pt];
@@ -205,19 +212,39 @@ template <class MT>
 static hipError_t launch_fd32_t(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
                                 TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
                                 CostDev cost, double* warm_c, double* cost_c, double* deriv, int Ds, double eps,
-                                hipStream_t st) {
+                                hipStream_t st, int cstride) {
   const size_t lds = coop_lds_bytes_f32(L, C);
-  hipError_t e = allow_lds32(reinterpret_cast<const void*>(k_fd_centre32<MT>), lds);
+  if (cstride) {
+    const int nctrl = m.nu < m.nv ? m.nu : m.nv;
+    const long blocks = (long)npts * (nctrl + 2 * m.nv);
+    hipError_t e = allow_lds32(reinterpret_cast<const void*>(k_fd_centre32<MT, int>), lds);
+    if (e != hipSuccess) return e;
+    e = allow_lds32(reinterpret_cast<const void*>(k_fd_cols32<MT, int>), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_fd_centre32<MT, int>), dim3(npts), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
+                       xfrc_applied, cost, warm_c, cost_c, cstride);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_fd_cols32<MT, int>), dim3((unsigned)blocks), dim3(TEAM32), lds, st, m, L, C, X, tr, P,
+                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, (float)eps, cstride);
+    return hipGetLastError();
+  }
+  // (typed: the kernels' trailing parameter pack is empty here)
+  void (*const kcen)(DevModel, WsLayout, coop::CoopLayout, coop::CoopAux, TrajDev, int, const double*, const double*,
+                     CostDev, double*, double*) = k_fd_centre32<MT>;
+  void (*const kcol)(DevModel, WsLayout, coop::CoopLayout, coop::CoopAux, TrajDev, int, const double*, const double*,
+                     CostDev, const double*, const double*, double*, int, float) = k_fd_cols32<MT>;
+  hipError_t e = allow_lds32(reinterpret_cast<const void*>(kcen), lds);
   if (e != hipSuccess) return e;
-  e = allow_lds32(reinterpret_cast<const void*>(k_fd_cols32<MT>), lds);
+  e = allow_lds32(reinterpret_cast<const void*>(kcol), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fd_centre32<MT>, dim3(npts), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
+  hipLaunchKernelGGL(kcen, dim3(npts), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
                      xfrc_applied, cost, warm_c, cost_c);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int nctrl = m.nu < m.nv ? m.nu : m.nv;
   const long blocks = (long)npts * (nctrl + 2 * m.nv);
-  hipLaunchKernelGGL(k_fd_cols32<MT>, dim3((unsigned)blocks), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
+  hipLaunchKernelGGL(kcol, dim3((unsigned)blocks), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
                      xfrc_applied, cost, warm_c, cost_c, deriv, Ds, (float)eps);
   return hipGetLastError();
 }
@@ -225,16 +252,16 @@ static hipError_t launch_fd32_t(const DevModel& m, const WsLayout& L, const coop
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
                                const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                               double* deriv, int Ds, double eps, hipStream_t st) {
+                               double* deriv, int Ds, double eps, hipStream_t st, int cstride) {
   if (npts <= 0) return hipSuccess;
   static const int nvc_env = [] {
     const char* v = getenv("ILQG_NV_CONST");
     return (v && v[0] == '0') ? 0 : 1;
   }();
   if (nvc_env && m.nv == 27) return launch_fd32_t<DevModelNV<27>>(m, L, C, X, tr, npts, P, qfrc_applied, xfrc_applied,
-                                                                 cost, warm_c, cost_c, deriv, Ds, eps, st);
+                                                                 cost, warm_c, cost_c, deriv, Ds, eps, st, cstride);
   return launch_fd32_t<DevModel>(m, L, C, X, tr, npts, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds,
-                                 eps, st);
+                                 eps, st, cstride);
 }
 
 }  // namespace ilqg

@@ -70,6 +70,7 @@ EXPORTS = [
     "ilqg_solver_join_stream", "ilqg_source_sha", "ilqg_forward_sharded", "ilqg_point_owners",
     "ilqg_solver_point_owners",
     "ilqg_model_ctrlrange", "ilqg_solver_set_ctrl_limits", "ilqg_solver_get_ctrl_limits", "ilqg_solver_get_clamped",
+    "ilqg_solver_set_cost_schedule", "ilqg_solver_get_cost_schedule", "ilqg_solver_shift_cost_schedule",
 ]
 KERNELS = ("rollout", "select", "fd_centre", "fd_cols", "backward", "fd_backward")
 
@@ -197,6 +198,11 @@ class Cost:
         return {k: arr(getattr(self, k), n) for k, n in
                 (("wq", nq), ("tq", nq), ("lq", nq), ("wv", nv), ("tv", nv), ("lv", nv),
                  ("wu", nu), ("tu", nu), ("lu", nu))}
+
+    def row(self, nq, nv, nu) -> np.ndarray:
+        """the cost as one cost-schedule row of 3 (nq + nv + nu) doubles, in
+        packed()'s order: wq tq lq wv tv lv wu tu lu (ILQR.set_cost_schedule)"""
+        return np.concatenate(list(self.packed(nq, nv, nu).values()))
 
     def struct(self, nq, nv, nu):
         p = self.packed(nq, nv, nu)
@@ -544,6 +550,52 @@ class ILQR:
         up = ctypes.POINTER(ctypes.c_uint)
         _check(lib().ilqg_solver_get_clamped(self._h, mask.ctypes.data_as(up), info.ctypes.data_as(up)), "get_clamped")
         return mask, info
+
+    def _cost_rows(self, rows, n=None) -> np.ndarray:
+        """(n, C) float64 rows from an array or a sequence of Costs"""
+        m = self.model
+        C = 3 * (m.nq + m.nv + m.nu)
+        if isinstance(rows, Cost):
+            rows = [rows]
+        if not isinstance(rows, np.ndarray) and len(rows) and all(isinstance(r, Cost) for r in rows):
+            rows = np.stack([r.row(m.nq, m.nv, m.nu) for r in rows])
+        rows = _f64(rows)
+        if rows.ndim == 1:
+            rows = rows.reshape(-1, C) if rows.size % C == 0 else rows
+        if rows.ndim != 2 or rows.shape[1] != C or (n is not None and rows.shape[0] != n):
+            raise IlqgError(f"cost rows must be ({'n' if n is None else n}, {C}), got {rows.shape}")
+        return rows
+
+    def set_cost_schedule(self, rows):
+        """cost schedule (ilqg_solver_set_cost_schedule; the reference has
+        none): point p of every seed's trajectory is charged with rows[p] in the
+        rollout and the FD sweep -- a reference that moves over the horizon,
+        and rows[0] as the terminal cost.  rows: an (N+1, C) array of packed
+        rows (Cost.row), a sequence of N+1 Costs, or None to switch it off."""
+        if rows is None:
+            _check(lib().ilqg_solver_set_cost_schedule(self._h, None), "set_cost_schedule")
+            return
+        rows = self._cost_rows(rows, self.P)
+        _check(lib().ilqg_solver_set_cost_schedule(self._h, _ptr(rows)), "set_cost_schedule")
+
+    def cost_schedule(self):
+        """the (N+1, C) rows in force, or None while no schedule is set
+        (ilqg_solver_get_cost_schedule)"""
+        m = self.model
+        rows = np.zeros((self.P, 3 * (m.nq + m.nv + m.nu)))
+        on = ctypes.c_int(0)
+        _check(lib().ilqg_solver_get_cost_schedule(self._h, _ptr(rows), ctypes.byref(on)), "get_cost_schedule")
+        return rows if on.value else None
+
+    def shift_cost_schedule(self, new_rows, n=None):
+        """the receding-horizon tick (ilqg_solver_shift_cost_schedule): the
+        window advances n steps (default: one per new row), row p takes row
+        p - n and rows 0 .. n-1 take new_rows (packed rows or Costs)"""
+        new_rows = self._cost_rows(new_rows)
+        n = new_rows.shape[0] if n is None else int(n)
+        if n >= 1 and new_rows.shape[0] != n:
+            raise IlqgError(f"shift_cost_schedule: {n} steps need {n} new rows, got {new_rows.shape[0]}")
+        _check(lib().ilqg_solver_shift_cost_schedule(self._h, n, _ptr(new_rows)), "shift_cost_schedule")
 
     def set_groups(self, ngroups: int):
         """seed groups (ilqg_solver_set_groups): iterate() software-pipelines

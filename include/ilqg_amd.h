@@ -253,6 +253,40 @@ int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* ena
    Point 0 (no step) and every entry after a pass without limits read 0.
    Synchronises.  No counterpart in the reference. */
 int ilqg_solver_get_clamped(ilqg_solver* s, unsigned* mask, unsigned* info);
+/* Cost schedule: one cost row per trajectory point, resident on the device and
+   shared by every seed; off by default.  No counterpart in the reference: it
+   stands in for a stepCostFn_t (inc/mjderivative.h:5) that reads d->time, i.e.
+   a running cost that moves over the horizon, and a terminal cost of its own.
+   rows: (N+1) x C doubles, C = 3 (nq + nv + nu); row p, the cost of point p, is
+   the ilqg_cost arrays packed as wq[nq] tq[nq] lq[nq] wv[nv] tv[nv] lv[nv]
+   wu[nu] tu[nu] lu[nu].  Point 0 is the terminal point (initV reads its
+   record, so row 0 is the terminal cost) and point N the first applied control.
+   NULL switches the feature off: the solver is then exactly as created.  Any
+   non-finite entry is ILQG_ERR_ARG.  Synchronises like ilqg_solver_set_mu and
+   applies to every launch enqueued after it.  With a schedule on:
+   - ilqg_forward (and the rollout inside ilqg_iterate / ilqg_forward_sharded)
+     charges a candidate with sum_n step_cost(row n; x_n, u_n), n = N .. 0, the
+     terms of a point in ilqg_cost's order; selection works on these costs.
+   - the FD sweep (fused, unfused, ilqg_fd_sweep_range, fp32) takes costCenter
+     and every perturbed cost of point p from row p.
+   - the Riccati engines consume records and are unchanged; the constructor's
+     passive rollout, ilqg_fd_batch and the legacy layer keep the creation cost.
+   Composes with both layouts, set_mu, set_value, set_deriv, control limits,
+   fp32 FD, the MFMA engine, seed groups (every group reads the same rows) and
+   ilqg_forward_sharded.  ILQG_ERR_UNSUPPORTED, from whichever call comes
+   second: from the forward calls when ILQG_DUAL=0 selects a rollout kernel
+   without a scheduled variant. */
+int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows);
+/* the rows in force, (N+1) x C, and whether a schedule is on; either pointer
+   may be NULL.  While off every row reads as the creation cost.  No counterpart
+   in the reference (it stands in for reading back such a stepCostFn_t's state). */
+int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled);
+/* the receding-horizon tick of a schedule: the window advances n steps, row p
+   takes row p - n for p >= n and rows 0 .. n-1 take new_rows (n x C).  No
+   counterpart in the reference: a stepCostFn_t that reads d->time follows the
+   advancing clock by itself.  ILQG_ERR_ARG while the schedule is off, for
+   n < 1 or n > N+1, and for new_rows NULL or non-finite.  Synchronises. */
+int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows);
 /* Riccati recursion (inc/ilqr.h:133-176) engine.  EXACT (default): the
    oracle's loops, bit-identical K, k, V, v (streamed behind the FD sweep on
    cooperative models).  MFMA: every matrix product (B'V, Quu = -2B'VB - 2R,
