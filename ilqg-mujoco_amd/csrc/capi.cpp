@@ -656,7 +656,6 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
   auto* m = const_cast<ilqg_model*>(mc);
   if (!m || n <= 0 || !qpos || !qvel || !warm || !ctrl || !deriv) return fail(ILQG_ERR_ARG, "bad argument");
   const HostModel& h = m->host;
-  const int nctrl = std::min(h.nu, h.nv), ncol = nctrl + 2 * h.nv;
   const int D = h.nv * (2 * h.nv + h.nu) + 2 * h.nv + h.nu;
   Scratch s;
   std::vector<double> t0(n, 0.0);
@@ -687,7 +686,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     a.tr = st; a.S = n; a.P = 1; a.nB = 0; a.nv = h.nv; a.nut = fd_nut(h);
     a.Dp = Dp; a.WCp = WCp; a.qfrc_applied = s.qa.as<double>(); a.xfrc_applied = s.xf.as<double>(); a.cost = cd;
     a.cw = cw.as<double>(); a.deriv = outp.as<double>(); a.sync = sy.as<unsigned>(); a.fault = fl.as<unsigned>();
-    HIPCHK(launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, m->stream));
+    HIPCHK(launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, m->stream, 0));
     HIPCHK(hipStreamSynchronize(m->stream));
     unsigned flt = 0;
     HIPCHK(hipMemcpy(&flt, fl.p, 4, hipMemcpyDeviceToHost));
@@ -695,10 +694,10 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     HIPCHK(hipMemcpy2D(deriv, (size_t)D * 8, outp.p, (size_t)Dp * 8, (size_t)D * 8, n, hipMemcpyDeviceToHost));
     return ILQG_OK;
   } else {
-    HIPCHK(launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd,
-                                 s.warm_c.as<double>(), s.cost_c.as<double>(), m->stream));
-    HIPCHK(launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd,
-                               s.warm_c.as<double>(), s.cost_c.as<double>(), s.out.as<double>(), D, m->stream));
+    const FdArgs fa{st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd, 0, s.warm_c.as<double>(),
+                    s.cost_c.as<double>(), s.out.as<double>(), D, m->stream};
+    HIPCHK(launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, fa));
+    HIPCHK(launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, fa));
   }
   HIPCHK(hipStreamSynchronize(m->stream));
   HIPCHK(hipMemcpy(deriv, s.out.p, (size_t)n * D * 8, hipMemcpyDeviceToHost));
@@ -843,9 +842,10 @@ int ilqg_solver_init(ilqg_solver* s, const double* time, const double* qpos, con
     HIPCHK(hipMemcpy(s->xfrc_applied.p, xfrc_applied, (size_t)s->S * 6 * h.nbody * 8, hipMemcpyHostToDevice));
   // ILQR ctor: passive rollout with constant ctrl into dArray[N..0]
   TrajDev nom = s->tview(s->traj), di = s->tview(s->dinit);
-  HIPCHK(launch_rollout_coop(m->dm, m->Lc, m->C, m->X, s->S, 1, s->P, nom, nom, 0, s->K.as<double>(),
-                             s->k.as<double>(), nullptr, di, s->qfrc_applied.as<double>(),
-                             s->xfrc_applied.as<double>(), 1, s->cview0(), nullptr, s->stream));
+  HIPCHK(launch_rollout_coop(m->dm, m->Lc, m->C, m->X,
+                             RollArgs{s->S, 1, s->P, nom, nom, 0, s->K.as<double>(), s->k.as<double>(), nullptr, di,
+                                      s->qfrc_applied.as<double>(), s->xfrc_applied.as<double>(), 1, s->cview0(),
+                                      nullptr, s->stream, RollChunk{}, 0}));
   HIPCHK(s->sync_all());
   // setDInit(dmain) as the MPC driver does before iterating (src/inverted_pendulum/inverted_pendulum.cpp:21)
   s->initialized = true;
@@ -958,49 +958,40 @@ static int limits_rollout_check(const ilqg_solver* s) {
 // rollout of every (seed, alpha) candidate of the range, then selection + setDInit
 static hipError_t rollout_launch(ilqg_solver* s, const SeedRange& r, RollChunk ch);
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st);
+// the range's views of the solver's buffers, as the rollout over ch's points takes them
+static RollArgs roll_args(ilqg_solver* s, const SeedRange& r, RollChunk ch) {
+  const HostModel& h = s->model->host;
+  const size_t s0 = r.s0, P = s->P, A = s->A, nx = s->nx;
+  const TrajDev nom = toff(s->tview(s->traj), s0 * P, h);
+  const bool multi = s->A > 1;
+  if (ch.n_hi >= 0) ch.carry = toff(s->tview(s->carry), s0 * A, h);
+  if (s->limits) ch.ulim = s->ulim.as<double>();
+  return RollArgs{r.ns, s->A, s->P, nom, multi ? toff(s->tview(s->cand), s0 * A * P, h) : nom, multi ? 1 : 0,
+                  s->K.as<double>() + s0 * P * h.nu * nx, s->k.as<double>() + s0 * P * h.nu, s->alphas.as<double>(),
+                  toff(s->tview(s->dinit), s0, h), s->qfrc_applied.as<double>() + s0 * h.nv,
+                  s->xfrc_applied.as<double>() + s0 * 6 * h.nbody, 0, s->cview(), s->cost_cand.as<double>() + s0 * A,
+                  r.st, ch, s->cstride()};
+}
 static hipError_t forward_range(ilqg_solver* s, const SeedRange& r, hipEvent_t before_select = nullptr) {
   const ilqg_model* m = s->model;
-  const HostModel& h = m->host;
-  const size_t s0 = r.s0, P = s->P, A = s->A, nx = s->nx;
-  TrajDev nom = toff(s->tview(s->traj), s0 * P, h), di = toff(s->tview(s->dinit), s0, h);
-  const bool multi = s->A > 1;
-  TrajDev outv = multi ? toff(s->tview(s->cand), s0 * A * P, h) : nom;
-  const double* K = s->K.as<double>() + s0 * P * h.nu * nx;
-  const double* k = s->k.as<double>() + s0 * P * h.nu;
-  const double* qa = s->qfrc_applied.as<double>() + s0 * h.nv;
-  const double* xf = s->xfrc_applied.as<double>() + s0 * 6 * h.nbody;
-  double* cc = s->cost_cand.as<double>() + s0 * A;
   hipError_t e = rollout_launch(s, r, RollChunk{});
   if (e != hipSuccess) return e;
   if (before_select) {
     e = hipStreamWaitEvent(r.st, before_select, 0);
     if (e != hipSuccess) return e;
   }
+  const RollArgs a = roll_args(s, r, RollChunk{});  // (the selection reads the same views)
   return s->timed(1, [&] {
-    return launch_select(m->dm, r.ns, s->A, s->P, s->opts.select_mode, multi ? 1 : 0, cc, s->sel.as<int>() + s0,
-                         s->cost_sel.as<double>() + s0, outv, nom, di, r.st);
+    return launch_select(m->dm, r.ns, s->A, s->P, s->opts.select_mode, a.out_is_cand, a.cost_cand,
+                         s->sel.as<int>() + r.s0, s->cost_sel.as<double>() + r.s0, a.out, a.nominal, a.dinit, r.st);
   }, r.st);
 }
 
 // the rollout of every (seed, alpha) candidate of the range over ch's points
 static hipError_t rollout_launch(ilqg_solver* s, const SeedRange& r, RollChunk ch) {
   const ilqg_model* m = s->model;
-  const HostModel& h = m->host;
-  const size_t s0 = r.s0, P = s->P, A = s->A, nx = s->nx;
-  TrajDev nom = toff(s->tview(s->traj), s0 * P, h), di = toff(s->tview(s->dinit), s0, h);
-  const bool multi = s->A > 1;
-  TrajDev outv = multi ? toff(s->tview(s->cand), s0 * A * P, h) : nom;
-  const double* K = s->K.as<double>() + s0 * P * h.nu * nx;
-  const double* k = s->k.as<double>() + s0 * P * h.nu;
-  const double* qa = s->qfrc_applied.as<double>() + s0 * h.nv;
-  const double* xf = s->xfrc_applied.as<double>() + s0 * 6 * h.nbody;
-  double* cc = s->cost_cand.as<double>() + s0 * A;
-  if (ch.n_hi >= 0) ch.carry = toff(s->tview(s->carry), s0 * A, h);
-  if (s->limits) ch.ulim = s->ulim.as<double>();
-  return s->timed(0, [&] {
-    return launch_rollout_coop(m->dm, m->Lc, m->C, m->X, r.ns, s->A, s->P, nom, outv, multi ? 1 : 0, K, k,
-                               s->alphas.as<double>(), di, qa, xf, 0, s->cview(), cc, r.st, ch, s->cstride());
-  }, r.st);
+  const RollArgs a = roll_args(s, r, ch);
+  return s->timed(0, [&] { return launch_rollout_coop(m->dm, m->Lc, m->C, m->X, a); }, r.st);
 }
 
 // the pipelined iterate's resources (ILQG_PIPE_STREAMS sweep streams CU-masked
@@ -1279,35 +1270,32 @@ static hipError_t fused_launch(ilqg_solver* s, const SeedRange& r, int mode, boo
   return launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, r.st, s->cstride());
 }
 
+// the two-kernel FD sweep (fp64 or fp32) of npts points from point p0 of seed
+// sd on, P points per seed as the kernels index them (pt / P, pt % P)
+static FdArgs fd_args(ilqg_solver* s, int sd, int p0, int npts, int P, hipStream_t st) {
+  const HostModel& h = s->model->host;
+  const size_t pt0 = (size_t)sd * s->P + p0;
+  return FdArgs{toff(s->tview(s->traj), pt0, h), npts, P, s->qfrc_applied.as<double>() + (size_t)sd * h.nv,
+                s->xfrc_applied.as<double>() + (size_t)sd * 6 * h.nbody, s->cview(p0), s->cstride(),
+                s->warm_c.as<double>() + pt0 * h.nv, s->cost_c.as<double>() + pt0,
+                s->deriv.as<double>() + pt0 * s->Dp, s->Dp, st};
+}
+
 int ilqg_fd_sweep(ilqg_solver* s) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
   s->grp_join = true;
   const ilqg_model* m = s->model;
-  TrajDev nom = s->tview(s->traj);
-  const int npts = s->S * s->P;
   if (s->fused) {
     HIPCHK(s->timed(3, [&] { return fused_launch(s, whole(s), 0); }));
     return ILQG_OK;
   }
+  const FdArgs a = fd_args(s, 0, 0, s->S * s->P, s->P, s->stream);
   if (s->fdprec == ILQG_FD_F32) {
-    HIPCHK(s->timed(3, [&] {
-      return launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
-                                 s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                                 s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, ILQG_FD32_EPS, s->stream,
-                                 s->cstride());
-    }));
+    HIPCHK(s->timed(3, [&] { return launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, a, ILQG_FD32_EPS); }));
     return ILQG_OK;
   }
-  HIPCHK(s->timed(2, [&] {
-    return launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
-                                 s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                                 s->cost_c.as<double>(), s->stream, s->cstride());
-  }));
-  HIPCHK(s->timed(3, [&] {
-    return launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, nom, npts, s->P, s->qfrc_applied.as<double>(),
-                               s->xfrc_applied.as<double>(), s->cview(), s->warm_c.as<double>(),
-                               s->cost_c.as<double>(), s->deriv.as<double>(), s->Dp, s->stream, s->cstride());
-  }));
+  HIPCHK(s->timed(2, [&] { return launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, a); }));
+  HIPCHK(s->timed(3, [&] { return launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, a); }));
   return ILQG_OK;
 }
 
@@ -1318,28 +1306,17 @@ int ilqg_fd_sweep(ilqg_solver* s) {
 // the same records the whole-trajectory sweep writes.
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st) {
   const ilqg_model* m = s->model;
-  const HostModel& h = m->host;
   // the kernels' seed index pt / P is 0 for every point of the range, and their
   // point index pt % P counts from p0: the cost schedule is passed from row p0 on
   constexpr int kOneSeed = 1 << 30;
   for (int sd = 0; sd < s->S; sd++) {
-    const size_t pt0 = (size_t)sd * s->P + p0;
-    const TrajDev nom = toff(s->tview(s->traj), pt0, h);
-    const double* qa = s->qfrc_applied.as<double>() + (size_t)sd * h.nv;
-    const double* xa = s->xfrc_applied.as<double>() + (size_t)sd * 6 * h.nbody;
-    double* wc = s->warm_c.as<double>() + pt0 * h.nv;
-    double* cc = s->cost_c.as<double>() + pt0;
-    double* dv = s->deriv.as<double>() + pt0 * s->Dp;
+    const FdArgs a = fd_args(s, sd, p0, np, kOneSeed, st);
     hipError_t e;
     if (s->fdprec == ILQG_FD_F32) {
-      e = launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, dv, s->Dp,
-                              ILQG_FD32_EPS, st, s->cstride());
+      e = launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, a, ILQG_FD32_EPS);
     } else {
-      e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, st,
-                                s->cstride());
-      if (e == hipSuccess)
-        e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, nom, np, kOneSeed, qa, xa, s->cview(p0), wc, cc, dv, s->Dp,
-                                st, s->cstride());
+      e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, a);
+      if (e == hipSuccess) e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, a);
     }
     if (e != hipSuccess) return e;
   }

@@ -8,12 +8,11 @@
 #include "dcoop.h"
 #include "handoff.h"
 #include "kernels.h"
+#include "launch.h"
 #include "static_models.h"
 
 namespace ilqg {
 namespace {
-
-using namespace coop;
 
 using namespace coop;
 
@@ -180,13 +179,60 @@ __device__ inline void load_state(const auto& m, const auto& L, const Team& T, c
   TSYNC();
 }
 
-template <typename K>
-hipError_t allow_lds(K kern, size_t lds) {
-  if (lds <= 65536) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds);
+// A kernel variant that takes one more argument is a template with a trailing
+// parameter pack: empty for the instances that exist without the variant (their
+// argument list, and so their code, is what it was), one type for those with.
+// SCH...: the cost schedule's row stride (kernels.h cost_at), `int`; the
+// bodies' `sched` tag is std::bool_constant<(sizeof...(SCH) > 0)>.
+__device__ constexpr int sched_stride() { return 0; }
+__device__ constexpr int sched_stride(int cstride) { return cstride; }
+
+// ---- host side (launch.h: allow_lds, launch, for_model_type) ----
+// The compiled specialisation of a bundled model (static_models.h), if any:
+// f(SM{}, SX{}) with its model and aux types; false = none, the generic kernel
+template <class F>
+bool for_static_model(int static_id, F&& f) {
+  switch (static_id) {
+#define ILQG_CASE(id, SMT, SXT) \
+  case id:                      \
+    f(stat::SMT{}, stat::SXT{}); \
+    return true;
+    ILQG_STATIC_MODELS(ILQG_CASE)
+#undef ILQG_CASE
+    default:
+      return false;
+  }
 }
 
+#ifdef ILQG_STAMPS
+// readers of this unit's copy of the diagnostic counters (dcoop_impl.h): the
+// line-search counters g_ls, and the stage stamps (tools/stamps.py)
+inline int debug_ls(unsigned long long* out5, int reset) {
+  if (hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_ls), sizeof(unsigned long long) * 8) != hipSuccess) return 3;
+  if (reset) {
+    unsigned long long z[8] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ls), z, sizeof(z));
+  }
+  return 0;
+}
+inline int debug_stamps(unsigned long long* acc, unsigned long long* cnt, int reset) {
+  if (hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_stamp_acc), sizeof(unsigned long long) * STAMP_NG) != hipSuccess) return 3;
+  if (hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_stamp_cnt), sizeof(unsigned long long) * STAMP_NG) != hipSuccess) return 3;
+  unsigned long long nw[2];
+  (void)hipMemcpyFromSymbol(&nw[0], HIP_SYMBOL(g_newton_iters), 8);
+  (void)hipMemcpyFromSymbol(&nw[1], HIP_SYMBOL(g_newton_calls), 8);
+  acc[44] = nw[0];
+  acc[45] = nw[1];
+  if (reset) {
+    unsigned long long z[STAMP_NG] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_newton_iters), z, 8);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_newton_calls), z, 8);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_acc), z, sizeof(z));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_cnt), z, sizeof(z));
+  }
+  return 0;
+}
+#endif
 
 }  // namespace
 }  // namespace ilqg

@@ -42,8 +42,8 @@ struct CostDev {
 // row 0 of a [point][3 (nq + nv + nu)] table, packed wq tq lq wv tv lv wu tu lu,
 // and point p is charged with the row `stride` doubles further on per point.
 // The launches below take the stride as `cstride` (0 = one stationary cost:
-// the kernels they always launched); != 0 launches the *_sch instances, which
-// carry it as an extra kernel argument.
+// the kernels they always launched); != 0 launches the kernels' scheduled
+// instances (<.., int>), which carry it as an extra last kernel argument.
 __host__ __device__ inline CostDev cost_at(const CostDev& c, int p, int stride) {
   const size_t o = (size_t)p * (size_t)stride;
   return CostDev{c.wq + o, c.tq + o, c.lq + o, c.wv + o, c.tv + o, c.lv + o, c.wu + o, c.tu + o, c.lu + o};
@@ -164,28 +164,48 @@ hipError_t launch_fd_order_check(int S, int P, int nt, unsigned* order, unsigned
 // ---- cooperative (one wavefront per evaluation, LDS workspace) variants ----
 namespace ilqg {
 size_t coop_lds_bytes(const WsLayout& L, const coop::CoopLayout& C);
+// an FD sweep over npts points, P per seed (kernels_fd.hip's two-kernel sweep,
+// kernels_fd32.hip): centre warm starts and costs into warm_c / cost_c, the
+// records into deriv at stride Ds
+struct FdArgs {
+  TrajDev tr;
+  int npts, P;
+  const double *qfrc_applied, *xfrc_applied;
+  CostDev cost;
+  int cstride;  // cost schedule (cost_at), 0 = none
+  double *warm_c, *cost_c;
+  double* deriv;
+  int Ds;
+  hipStream_t st;
+};
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                                 const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
-                                 const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                                 hipStream_t st, int cstride = 0);
+                                 const coop::CoopAux& X, const FdArgs& a);
 hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                               const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
-                               const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c,
-                               double* deriv, int Ds, hipStream_t st, int cstride = 0);
+                               const coop::CoopAux& X, const FdArgs& a);
 // fp32 FD sweep (kernels_fd32.hip; BASELINE.json configs[4]): centre + column
 // kernels on the fp32 physics, fp64 records; eps is the FD step (1e-3)
 size_t coop_lds_bytes_f32(const WsLayout& L, const coop::CoopLayout& C);
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                               const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
-                               const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                               double* deriv, int Ds, double eps, hipStream_t st, int cstride = 0);
+                               const coop::CoopAux& X, const FdArgs& a, double eps);
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                                const coop::CoopAux& X, const FdFused& a, hipStream_t st, int cstride = 0);
+                                const coop::CoopAux& X, const FdFused& a, hipStream_t st, int cstride);
+// a rollout of S seeds x A candidates over a P-point horizon (ch: the points)
+struct RollArgs {
+  int S, A, P;
+  TrajDev nominal, out;
+  int out_is_cand;
+  const double *K, *k, *alphas;
+  TrajDev dinit;
+  const double *qfrc_applied, *xfrc_applied;
+  int passive;
+  CostDev cost;
+  double* cost_cand;
+  hipStream_t st;
+  RollChunk ch;
+  int cstride;  // cost schedule (cost_at), 0 = none
+};
 hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                               const coop::CoopAux& X, int S, int A, int P, TrajDev nominal, TrajDev out,
-                               int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit,
-                               const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost,
-                               double* cost_cand, hipStream_t st, RollChunk ch = RollChunk{}, int cstride = 0);
+                               const coop::CoopAux& X, const RollArgs& a);
 // whether the rollout kernel this process selects (ILQG_DUAL) has a clamped
 // variant (RollChunk.ulim): launch_rollout_coop refuses limits otherwise
 bool rollout_clamp_supported();

@@ -12,9 +12,10 @@
 namespace ilqg {
 namespace {
 
-// sched (the *_sch kernels, launched while a cost schedule is set,
-// kernels.h cost_at): the point's costs are taken from its own row of the
-// schedule, `cstride` doubles per point past the descriptor's arrays
+// sched (the kernels' <.., int> instances, launched while a cost schedule is
+// set, kernels.h cost_at; SCH... in coop_common.h): the point's costs are taken
+// from its own row of the schedule, `cstride` doubles per point past the
+// descriptor's arrays
 __device__ inline void fd_centre_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
                                 TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
                                 auto sched, int cstride) {
@@ -31,24 +32,25 @@ __device__ inline void fd_centre_body(const auto& m, const auto& L, const auto& 
   STAMP_FLUSH();
 }
 
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c) {
+template <class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, SCH... cstride) {
   Team T = make_team(L, C);
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::false_type{}, 0);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c) {
+template <class SM, class SX, class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, SCH... cstride) {
   static constexpr WsLayout L = make_layout(SM{}, SX::npair);
   static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
   static constexpr SX X{};
   Team T = make_team(L, C);
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::false_type{}, 0);
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
 __device__ inline void fd_cols_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
@@ -137,24 +139,25 @@ __device__ inline void fd_cols_body(const auto& m, const auto& L, const auto& C,
   STAMP_FLUSH();
 }
 
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds) {
+template <class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, SCH... cstride) {
   Team T = make_team(L, C);
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::false_type{}, 0);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds) {
+template <class SM, class SX, class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, SCH... cstride) {
   static constexpr WsLayout L = make_layout(SM{}, SX::npair);
   static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
   static constexpr SX X{};
   Team T = make_team(L, C);
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::false_type{}, 0);
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
 // ---- fused FD sweep with the backward pass streamed behind it ------------
@@ -293,7 +296,6 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
   }
 #endif
   const int nv = m.nv, nu = m.nu, nq = m.nq;
-  const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   int role, s, p, idx, half;
   const int ntm = a.nut + 2 * nv;
   fd_decode(a, ntm, u, role, s, p, idx, half);
@@ -608,7 +610,8 @@ __device__ inline void fd_backward_role(const MD& mg, const FdFused& a, int s) {
 #endif
 }
 
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, FdFused a) {
+template <class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, FdFused a, SCH... cstride) {
   const unsigned t = take_ticket(a.sync);
   if (t < (unsigned)a.nB) {
     fd_backward_role<0, 0>(mg, a, (int)t);
@@ -618,14 +621,14 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevMode
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::false_type{}, 0);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
 // compile-time models: the model read from its global image (L1/L2 cached)
 // rather than an LDS copy, so the team's LDS holds only the workspace (8 teams
 // per CU for the hopper instead of 7)
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel mg, FdFused a) {
+template <class SM, class SX, class... SCH>
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel mg, FdFused a, SCH... cstride) {
   const unsigned t = take_ticket(a.sync);
   if (t < (unsigned)a.nB) {
     fd_backward_role<SM::nv, SM::nu>(mg, a, (int)t);
@@ -640,75 +643,20 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
   T.ci = T.iw + L.ni;
   SM m;
   m.bind(mg.img, mg);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::false_type{}, 0);
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
 }
 
-// ---- the cost-schedule instances of the kernels above: the same bodies with
-// the `sched` tag, the row stride as their last argument
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int cstride) {
-  Team T = make_team(L, C);
-  DevModel m;
-  CoopAux X;
-  stage_model(mg, Xg, L, C, T, m, X);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::true_type{}, cstride);
-}
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s_sch(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int cstride) {
-  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
-  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
-  static constexpr SX X{};
-  Team T = make_team(L, C);
-  SM m;
-  stage_model_s(mg, L, C, T, m);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::true_type{}, cstride);
-}
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int cstride) {
-  Team T = make_team(L, C);
-  DevModel m;
-  CoopAux X;
-  stage_model(mg, Xg, L, C, T, m, X);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::true_type{}, cstride);
-}
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s_sch(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int cstride) {
-  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
-  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
-  static constexpr SX X{};
-  Team T = make_team(L, C);
-  SM m;
-  stage_model_s(mg, L, C, T, m);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::true_type{}, cstride);
-}
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop_sch(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, FdFused a, int cstride) {
-  const unsigned t = take_ticket(a.sync);
-  if (t < (unsigned)a.nB) {
-    fd_backward_role<0, 0>(mg, a, (int)t);
-    return;
-  }
-  Team T = make_team(L, C);
-  DevModel m;
-  CoopAux X;
-  stage_model(mg, Xg, L, C, T, m, X);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::true_type{}, cstride);
-}
-template <class SM, class SX>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g_sch(DevModel mg, FdFused a, int cstride) {
-  const unsigned t = take_ticket(a.sync);
-  if (t < (unsigned)a.nB) {
-    fd_backward_role<SM::nv, SM::nu>(mg, a, (int)t);
-    return;
-  }
-  static constexpr WsLayout L = make_layout(SM{}, SX::npair);
-  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
-  static constexpr SX X{};
-  extern __shared__ double lds[];
-  Team T = make_team(L, C);
-  T.iw = reinterpret_cast<int*>(lds + L.nd + C.nd);  // no image region
-  T.ci = T.iw + L.ni;
-  SM m;
-  m.bind(mg.img, mg);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::true_type{}, cstride);
-}
+// The generic kernels' instances, instantiated here and in this order.  They
+// share the run-time model's physics functions, and which of them the inliner
+// reaches last, and gives the last copy of a shared function to, follows the
+// order of instantiation: left to the launchers' order of use,
+// k_fd_fused_coop grew by 10k instructions and 120 SGPR spills.
+template __global__ void k_fd_centre_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*);
+template __global__ void k_fd_cols_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int);
+template __global__ void k_fd_fused_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused);
+template __global__ void k_fd_centre_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int);
+template __global__ void k_fd_cols_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int);
+template __global__ void k_fd_fused_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused, int);
 
 // ---- the fused sweep's ticket schedule (launch_fd_plan) -----------------
 // One 1024-thread workgroup.  Items: centre C(s,p) = p S + s (u < S P), column
@@ -850,146 +798,71 @@ hipError_t launch_fd_order_check(int S, int P, int nt, unsigned* order, unsigned
 size_t coop_lds_bytes(const WsLayout& L, const CoopLayout& C) {
   return (size_t)(L.nd + C.nd + C.imgd) * sizeof(double) + (size_t)(L.ni + C.ni) * sizeof(int);
 }
+
+// Each launch below: the grid and the LDS, then the bundled model's instance or
+// the generic kernel; cs... is the cost schedule's stride (SCH = int) or empty.
+template <class... SCH>
+static hipError_t fd_centre(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
+                            const FdArgs& a, SCH... cs) {
+  const size_t lds = coop_lds_bytes(L, C);
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        e = launch(k_fd_centre_s<decltype(sm), decltype(sx), SCH...>, a.npts, TEAM, lds, a.st, m, a.tr, a.P,
+                   a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+      }))
+    return e;
+  return launch(k_fd_centre_coop<SCH...>, a.npts, TEAM, lds, a.st, m, L, C, X, a.tr, a.P, a.qfrc_applied,
+                a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+}
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
-                                 TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
-                                 CostDev cost, double* warm_c, double* cost_c, hipStream_t st, int cstride) {
-  if (npts <= 0) return hipSuccess;
-  const size_t lds = coop_lds_bytes(L, C);
-  hipError_t e;
-  if (cstride) {
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_centre_s_sch<stat::SMT, stat::SXT>, lds);                                                \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_centre_s_sch<stat::SMT, stat::SXT>), dim3(npts), dim3(TEAM), lds, st, m, tr, P,     \
-                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, cstride);                              \
-    return hipGetLastError();
-    switch (m.static_id) {
-      ILQG_STATIC_MODELS(ILQG_CASE)
-      default:
-        break;
-    }
-#undef ILQG_CASE
-    e = allow_lds(k_fd_centre_coop_sch, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fd_centre_coop_sch, dim3(npts), dim3(TEAM), lds, st, m, L, C, X, tr, P, qfrc_applied,
-                       xfrc_applied, cost, warm_c, cost_c, cstride);
-    return hipGetLastError();
-  }
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_centre_s<stat::SMT, stat::SXT>, lds);                                                    \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_centre_s<stat::SMT, stat::SXT>), dim3(npts), dim3(TEAM), lds, st, m, tr, P,         \
-                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c);                                       \
-    return hipGetLastError();
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_fd_centre_coop, coop_lds_bytes(L, C));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fd_centre_coop, dim3(npts), dim3(TEAM), coop_lds_bytes(L, C), st, m, L, C, X, tr, P,
-                     qfrc_applied, xfrc_applied, cost, warm_c, cost_c);
-  return hipGetLastError();
+                                 const FdArgs& a) {
+  if (a.npts <= 0) return hipSuccess;
+  return a.cstride ? fd_centre(m, L, C, X, a, a.cstride) : fd_centre(m, L, C, X, a);
 }
 
+template <class... SCH>
+static hipError_t fd_cols(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
+                          const FdArgs& a, unsigned blocks, SCH... cs) {
+  const size_t lds = coop_lds_bytes(L, C);
+  const double *warm_c = a.warm_c, *cost_c = a.cost_c;
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        e = launch(k_fd_cols_s<decltype(sm), decltype(sx), SCH...>, blocks, TEAM, lds, a.st, m, a.tr, a.P,
+                   a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, cs...);
+      }))
+    return e;
+  return launch(k_fd_cols_coop<SCH...>, blocks, TEAM, lds, a.st, m, L, C, X, a.tr, a.P, a.qfrc_applied,
+                a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, cs...);
+}
 hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
-                               TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
-                               CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds,
-                               hipStream_t st, int cstride) {
+                               const FdArgs& a) {
   const int nctrl = m.nu < m.nv ? m.nu : m.nv;
-  const long blocks = (long)npts * (nctrl + 2 * m.nv);
+  const long blocks = (long)a.npts * (nctrl + 2 * m.nv);
   if (blocks <= 0) return hipSuccess;
-  const size_t lds = coop_lds_bytes(L, C);
-  hipError_t e;
-  if (cstride) {
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_cols_s_sch<stat::SMT, stat::SXT>, lds);                                                  \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_cols_s_sch<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds, st, m,  \
-                       tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, cstride);            \
-    return hipGetLastError();
-    switch (m.static_id) {
-      ILQG_STATIC_MODELS(ILQG_CASE)
-      default:
-        break;
-    }
-#undef ILQG_CASE
-    e = allow_lds(k_fd_cols_coop_sch, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fd_cols_coop_sch, dim3((unsigned)blocks), dim3(TEAM), lds, st, m, L, C, X, tr, P,
-                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, cstride);
-    return hipGetLastError();
-  }
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_cols_s<stat::SMT, stat::SXT>, lds);                                                      \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_cols_s<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds, st, m, tr,  \
-                       P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds);                         \
-    return hipGetLastError();
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_fd_cols_coop, coop_lds_bytes(L, C));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fd_cols_coop, dim3((unsigned)blocks), dim3(TEAM), coop_lds_bytes(L, C), st, m, L, C, X, tr, P,
-                     qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds);
-  return hipGetLastError();
+  return a.cstride ? fd_cols(m, L, C, X, a, (unsigned)blocks, a.cstride) : fd_cols(m, L, C, X, a, (unsigned)blocks);
 }
 
+template <class... SCH>
+static hipError_t fd_fused(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
+                           const FdFused& a, unsigned blocks, hipStream_t st, SCH... cs) {
+  // the backward roles' LDS too; k_fd_fused_g keeps no model image in LDS
+  const size_t bw = a.nB > 0 ? backward_lds_bytes(m.nv, m.nu) : (size_t)0;
+  const size_t lds = std::max(coop_lds_bytes(L, C), bw);
+  const size_t lds_g = std::max((size_t)(L.nd + C.nd) * sizeof(double) + (size_t)(L.ni + C.ni) * sizeof(int), bw);
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        e = launch(k_fd_fused_g<decltype(sm), decltype(sx), SCH...>, blocks, TEAM, lds_g, st, m, a, cs...);
+      }))
+    return e;
+  return launch(k_fd_fused_coop<SCH...>, blocks, TEAM, lds, st, m, L, C, X, a, cs...);
+}
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                 const FdFused& a, hipStream_t st, int cstride) {
   const long items = (long)a.S * a.P * (1 + (a.halves ? 2 : 1) * (a.nut + 2 * m.nv));
   const long blocks = items + a.nB;
   if (items <= 0) return hipSuccess;
-  size_t lds = coop_lds_bytes(L, C);
-  if (a.nB > 0) lds = std::max(lds, backward_lds_bytes(m.nv, m.nu));
-  hipError_t e;
-  const size_t lds_g = std::max((size_t)(L.nd + C.nd) * sizeof(double) + (size_t)(L.ni + C.ni) * sizeof(int),
-                                a.nB > 0 ? backward_lds_bytes(m.nv, m.nu) : (size_t)0);
-  if (cstride) {
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_fused_g_sch<stat::SMT, stat::SXT>, lds_g);                                               \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_fused_g_sch<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds_g, st, \
-                       m, a, cstride);                                                                          \
-    return hipGetLastError();
-    switch (m.static_id) {
-      ILQG_STATIC_MODELS(ILQG_CASE)
-      default:
-        break;
-    }
-#undef ILQG_CASE
-    e = allow_lds(k_fd_fused_coop_sch, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fd_fused_coop_sch, dim3((unsigned)blocks), dim3(TEAM), lds, st, m, L, C, X, a, cstride);
-    return hipGetLastError();
-  }
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_fd_fused_g<stat::SMT, stat::SXT>, lds_g);                                                   \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_fd_fused_g<stat::SMT, stat::SXT>), dim3((unsigned)blocks), dim3(TEAM), lds_g, st, m, a); \
-    return hipGetLastError();
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_fd_fused_coop, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fd_fused_coop, dim3((unsigned)blocks), dim3(TEAM), lds, st, m, L, C, X, a);
-  return hipGetLastError();
+  return cstride ? fd_fused(m, L, C, X, a, (unsigned)blocks, st, cstride)
+                 : fd_fused(m, L, C, X, a, (unsigned)blocks, st);
 }
 
 }  // namespace ilqg
@@ -1022,36 +895,9 @@ extern "C" int ilqg_debug_fused(unsigned long long* d, int reset) {
   }
   return 0;
 }
-#endif
-
-#ifdef ILQG_STAMPS
-// the FD kernels' line-search counters (dcoop_impl.h g_ls)
-extern "C" int ilqg_debug_ls_fd(unsigned long long* out5, int reset) {
-  if (hipMemcpyFromSymbol(out5, HIP_SYMBOL(ilqg::coop::g_ls), sizeof(unsigned long long) * 8) != hipSuccess) return 3;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_ls), z, sizeof(z));
-  }
-  return 0;
-}
-// the FD kernels' copy of the stamp counters (tools/stamps.py)
+// the FD kernels' copy of the line-search and stamp counters (coop_common.h)
+extern "C" int ilqg_debug_ls_fd(unsigned long long* out5, int reset) { return ilqg::debug_ls(out5, reset); }
 extern "C" int ilqg_debug_stamps_fd(unsigned long long* acc, unsigned long long* cnt, int reset) {
-  if (hipMemcpyFromSymbol(acc, HIP_SYMBOL(ilqg::coop::g_stamp_acc), sizeof(unsigned long long) * STAMP_NG) != hipSuccess)
-    return 3;
-  if (hipMemcpyFromSymbol(cnt, HIP_SYMBOL(ilqg::coop::g_stamp_cnt), sizeof(unsigned long long) * STAMP_NG) != hipSuccess)
-    return 3;
-  unsigned long long nw[2];
-  (void)hipMemcpyFromSymbol(&nw[0], HIP_SYMBOL(ilqg::coop::g_newton_iters), 8);
-  (void)hipMemcpyFromSymbol(&nw[1], HIP_SYMBOL(ilqg::coop::g_newton_calls), 8);
-  acc[44] = nw[0];
-  acc[45] = nw[1];
-  if (reset) {
-    unsigned long long z[STAMP_NG] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_newton_iters), z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_newton_calls), z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_stamp_acc), z, sizeof(z));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_stamp_cnt), z, sizeof(z));
-  }
-  return 0;
+  return ilqg::debug_stamps(acc, cnt, reset);
 }
 #endif

@@ -11,6 +11,7 @@
 // stated tolerance against the fp64 oracle at the same eps.
 #include "dcoop_f32.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace ilqg {
 namespace {
@@ -203,65 +204,28 @@ size_t coop_lds_bytes_f32(const WsLayout& L, const coop::CoopLayout& C) {
   return (size_t)(L.nd + C.nd) * sizeof(float) + (size_t)(L.ni + C.ni) * sizeof(int);
 }
 
-static hipError_t allow_lds32(const void* kern, size_t lds) {
-  if (lds <= 65536) return hipSuccess;
-  return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-template <class MT>
-static hipError_t launch_fd32_t(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
-                                TrajDev tr, int npts, int P, const double* qfrc_applied, const double* xfrc_applied,
-                                CostDev cost, double* warm_c, double* cost_c, double* deriv, int Ds, double eps,
-                                hipStream_t st, int cstride) {
+// cs...: the cost schedule's stride (SCH = int) or empty
+template <class... SCH>
+static hipError_t fd_sweep32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
+                             const FdArgs& a, float eps, SCH... cs) {
   const size_t lds = coop_lds_bytes_f32(L, C);
-  if (cstride) {
-    const int nctrl = m.nu < m.nv ? m.nu : m.nv;
-    const long blocks = (long)npts * (nctrl + 2 * m.nv);
-    hipError_t e = allow_lds32(reinterpret_cast<const void*>(k_fd_centre32<MT, int>), lds);
-    if (e != hipSuccess) return e;
-    e = allow_lds32(reinterpret_cast<const void*>(k_fd_cols32<MT, int>), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_fd_centre32<MT, int>), dim3(npts), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
-                       xfrc_applied, cost, warm_c, cost_c, cstride);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_fd_cols32<MT, int>), dim3((unsigned)blocks), dim3(TEAM32), lds, st, m, L, C, X, tr, P,
-                       qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, (float)eps, cstride);
-    return hipGetLastError();
-  }
-  // (typed: the kernels' trailing parameter pack is empty here)
-  void (*const kcen)(DevModel, WsLayout, coop::CoopLayout, coop::CoopAux, TrajDev, int, const double*, const double*,
-                     CostDev, double*, double*) = k_fd_centre32<MT>;
-  void (*const kcol)(DevModel, WsLayout, coop::CoopLayout, coop::CoopAux, TrajDev, int, const double*, const double*,
-                     CostDev, const double*, const double*, double*, int, float) = k_fd_cols32<MT>;
-  hipError_t e = allow_lds32(reinterpret_cast<const void*>(kcen), lds);
-  if (e != hipSuccess) return e;
-  e = allow_lds32(reinterpret_cast<const void*>(kcol), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kcen, dim3(npts), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
-                     xfrc_applied, cost, warm_c, cost_c);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
   const int nctrl = m.nu < m.nv ? m.nu : m.nv;
-  const long blocks = (long)npts * (nctrl + 2 * m.nv);
-  hipLaunchKernelGGL(kcol, dim3((unsigned)blocks), dim3(TEAM32), lds, st, m, L, C, X, tr, P, qfrc_applied,
-                     xfrc_applied, cost, warm_c, cost_c, deriv, Ds, (float)eps);
-  return hipGetLastError();
+  const long blocks = (long)a.npts * (nctrl + 2 * m.nv);
+  const double *warm_c = a.warm_c, *cost_c = a.cost_c;
+  return for_model_type<DevModelNV>(m, [&](auto mt) {
+    using MT = typename decltype(mt)::type;
+    hipError_t e = launch(k_fd_centre32<MT, SCH...>, a.npts, TEAM32, lds, a.st, m, L, C, X, a.tr, a.P,
+                          a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+    if (e != hipSuccess) return e;
+    return launch(k_fd_cols32<MT, SCH...>, (unsigned)blocks, TEAM32, lds, a.st, m, L, C, X, a.tr, a.P,
+                  a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, eps, cs...);
+  });
 }
 
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                               const coop::CoopAux& X, TrajDev tr, int npts, int P, const double* qfrc_applied,
-                               const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                               double* deriv, int Ds, double eps, hipStream_t st, int cstride) {
-  if (npts <= 0) return hipSuccess;
-  static const int nvc_env = [] {
-    const char* v = getenv("ILQG_NV_CONST");
-    return (v && v[0] == '0') ? 0 : 1;
-  }();
-  if (nvc_env && m.nv == 27) return launch_fd32_t<DevModelNV<27>>(m, L, C, X, tr, npts, P, qfrc_applied, xfrc_applied,
-                                                                 cost, warm_c, cost_c, deriv, Ds, eps, st, cstride);
-  return launch_fd32_t<DevModel>(m, L, C, X, tr, npts, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds,
-                                 eps, st, cstride);
+                               const coop::CoopAux& X, const FdArgs& a, double eps) {
+  if (a.npts <= 0) return hipSuccess;
+  return a.cstride ? fd_sweep32(m, L, C, X, a, (float)eps, a.cstride) : fd_sweep32(m, L, C, X, a, (float)eps);
 }
 
 }  // namespace ilqg

@@ -1,11 +1,13 @@
 // Cooperative rollout kernels (inc/ilqr.h:116-130): one workgroup per
-// (seed, alpha) candidate; two-wave teams (step_dual) by default.  The variants
-// that charge a cost schedule are in kernels_rollout_sch.hip.
+// (seed, alpha) candidate; two-wave teams (step_dual) by default: k_rollout2_s
+// and k_rollout2_coop (rollout_body.h), whose instances without a cost schedule
+// this unit launches; kernels_rollout_sch.hip launches the scheduled ones.
 #include "rollout_body.h"
 
 namespace ilqg {
 namespace {
 
+// one-wave teams (ILQG_DUAL=0)
 __global__ __launch_bounds__(TEAM) void k_rollout_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
   Team T = make_team(L, C);
   DevModel m;
@@ -26,56 +28,6 @@ __global__ __launch_bounds__(TEAM) void k_rollout_s(DevModel mg, int S, int A, i
   rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch, -1, std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
 }
 
-// two-wave teams (step_dual): 128 threads per (seed, candidate).  MT: DevModel,
-// or DevModelNV<27> for 27-dof models (the humanoid: compile-time sizes in the
-// Newton Cholesky and its substitution)
-template <class MT>
-__global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
-  Team T = make_team(L, C);
-  MT m;
-  CoopAux X;
-  stage_model(mg, Xg, L, C, T, m, X);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
-               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
-               std::false_type{}, std::false_type{});
-}
-// k_rollout2_coop with the control law clamped to the solver's control limits (RollChunk.ulim)
-template <class MT>
-__global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop_lim(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
-  Team T = make_team(L, C);
-  MT m;
-  CoopAux X;
-  stage_model(mg, Xg, L, C, T, m, X);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
-               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
-               std::true_type{}, std::false_type{});
-}
-// three-wave teams for the compile-time register-row models (rollout_waves)
-template <class SM, class SX>
-__global__ __launch_bounds__(3 * TEAM) void k_rollout2_s(DevModel mg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
-  static constexpr WsLayout L = make_layout(SM{}, SX::npair, true);
-  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
-  static constexpr SX X{};
-  Team T = make_team(L, C);
-  SM m;
-  stage_model_sep(mg, T, m);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
-               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
-               std::false_type{}, std::false_type{}, std::false_type{});
-}
-// k_rollout2_s with the control law clamped to the solver's control limits (RollChunk.ulim)
-template <class SM, class SX>
-__global__ __launch_bounds__(3 * TEAM) void k_rollout2_s_lim(DevModel mg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch) {
-  static constexpr WsLayout L = make_layout(SM{}, SX::npair, true);
-  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
-  static constexpr SX X{};
-  Team T = make_team(L, C);
-  SM m;
-  stage_model_sep(mg, T, m);
-  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
-               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
-               std::false_type{}, std::true_type{}, std::false_type{});
-}
 // ---- batch physics (ilqg_step_batch / ilqg_forward_batch): one wavefront per state
 // mj_step x nstep from each state (cpMjData in, the state out)
 __device__ inline void step_batch_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
@@ -199,135 +151,29 @@ static bool use_dual() {
   }
   return v == 1;
 }
-hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X, int S,
-                               int A, int P, TrajDev nominal, TrajDev out, int out_is_cand, const double* K,
-                               const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied,
-                               const double* xfrc_applied, int passive, CostDev cost, double* cost_cand,
-                               hipStream_t st, RollChunk ch, int cstride) {
-  const size_t lds = rollout_lds(coop_lds_bytes(L, C));
-  hipError_t e;
-  // control limits: the clamped variants of the default kernels (k_rollout2_s,
+hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
+                               const RollArgs& a) {
+  // control limits: the clamped instances of the default kernels (k_rollout2_s,
   // k_rollout2_coop); the passive constructor rollout has no control law
-  const bool lim = ch.ulim != nullptr && !passive;
+  const bool lim = a.ch.ulim != nullptr && !a.passive;
   if (lim && !use_dual()) return hipErrorNotSupported;
-  // cost schedule: the scheduled variants of the same kernels, clamped or not
-  const bool sch = cstride != 0 && !passive;
+  // cost schedule: the scheduled instances of the same kernels, clamped or not
+  const bool sch = a.cstride != 0 && !a.passive;
   if (sch && !use_dual()) return hipErrorNotSupported;
-  const RollArgs ra{S, A, P, nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost,
-                    cost_cand, st, ch, cstride};
-  if (sch) {
-    bool done = false;
-    e = launch_rollout_sch_static(m, C, ra, lim, done);
-    if (done) return e;
-  } else if (lim) {
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id: {                                                                                                    \
-    const size_t lds2 = rollout_lds(coop_lds_bytes(make_layout(stat::SMT{}, stat::SXT::npair, true), C));       \
-    e = allow_lds(k_rollout2_s_lim<stat::SMT, stat::SXT>, lds2);                                                \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_rollout2_s_lim<stat::SMT, stat::SXT>), dim3(S * A),                                   \
-                       dim3(rollout_waves<stat::SMT>() * TEAM), lds2, st, m, S, A, P,                            \
-                       nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, \
-                       cost_cand, ch);                                                                              \
-    return hipGetLastError();                                                                                   \
-  }
-    switch (m.static_id) {
-      ILQG_STATIC_MODELS(ILQG_CASE)
-      default:
-        break;
-    }
-#undef ILQG_CASE
-  }
-  if (use_dual()) {
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id: {                                                                                                    \
-    const size_t lds2 = rollout_lds(coop_lds_bytes(make_layout(stat::SMT{}, stat::SXT::npair, true), C));       \
-    e = allow_lds(k_rollout2_s<stat::SMT, stat::SXT>, lds2);                                                    \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_rollout2_s<stat::SMT, stat::SXT>), dim3(S * A),                                       \
-                       dim3(rollout_waves<stat::SMT>() * TEAM), lds2, st, m, S, A, P,                            \
-                       nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, \
-                       cost_cand, ch);                                                                              \
-    return hipGetLastError();                                                                                   \
-  }
-    switch (m.static_id) {
-      ILQG_STATIC_MODELS(ILQG_CASE)
-      default:
-        break;
-    }
-#undef ILQG_CASE
-    // the record's second buffer past the workspace when it fits (RollChunk.dbuf;
-    // ILQG_ROLL_DBUF=0 keeps the register prefetch, A/B)
-    size_t lds_d = lds;
-    {
-      static const int dbuf_env = [] {
-        const char* v = getenv("ILQG_ROLL_DBUF");
-        return (v && v[0] == '0') ? 0 : 1;
-      }();
-      const size_t R = (size_t)m.nq + m.nv + m.nu + (size_t)m.nu * 2 * m.nv + m.nu;
-      const size_t need = (coop_lds_bytes(L, C) + 15) / 16 * 16 + R * sizeof(double);
-      if (dbuf_env && need <= 160 * 1024) {
-        ch.dbuf = 1;
-        lds_d = need > lds ? need : lds;
-      }
-    }
-    static const int nvc_env = [] {
-      const char* v = getenv("ILQG_NV_CONST");
-      return (v && v[0] == '0') ? 0 : 1;
-    }();
-    const bool nv27 = nvc_env && m.nv == 27;
-    const void* kf = nv27 ? reinterpret_cast<const void*>(k_rollout2_coop<DevModelNV<27>>)
-                          : reinterpret_cast<const void*>(k_rollout2_coop<DevModel>);
-    e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-    if (e != hipSuccess) return e;
-    if (sch) {
-      RollArgs rd = ra;
-      rd.ch = ch;  // (dbuf set above)
-      return launch_rollout_sch_generic(m, L, C, X, rd, lim, nv27, lds_d);
-    }
-    if (lim) {
-      const void* kl = nv27 ? reinterpret_cast<const void*>(k_rollout2_coop_lim<DevModelNV<27>>)
-                            : reinterpret_cast<const void*>(k_rollout2_coop_lim<DevModel>);
-      e = hipFuncSetAttribute(kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-      if (e != hipSuccess) return e;
-      if (nv27)
-        hipLaunchKernelGGL(k_rollout2_coop_lim<DevModelNV<27>>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S,
-                           A, P, nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive,
-                           cost, cost_cand, ch);
-      else
-        hipLaunchKernelGGL(k_rollout2_coop_lim<DevModel>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S, A, P,
-                           nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost,
-                           cost_cand, ch);
-      return hipGetLastError();
-    }
-    if (nv27)
-      hipLaunchKernelGGL(k_rollout2_coop<DevModelNV<27>>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S, A,
-                         P, nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost,
-                         cost_cand, ch);
-    else
-    hipLaunchKernelGGL(k_rollout2_coop<DevModel>, dim3(S * A), dim3(2 * TEAM), lds_d, st, m, L, C, X, S, A, P, nominal, out,
-                       out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch);
-    return hipGetLastError();
-  }
-#define ILQG_CASE(id, SMT, SXT)                                                                                 \
-  case id:                                                                                                      \
-    e = allow_lds(k_rollout_s<stat::SMT, stat::SXT>, lds);                                                      \
-    if (e != hipSuccess) return e;                                                                              \
-    hipLaunchKernelGGL((k_rollout_s<stat::SMT, stat::SXT>), dim3(S * A), dim3(TEAM), lds, st, m, S, A, P,        \
-                       nominal, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, \
-                       cost_cand, ch);                                                                              \
-    return hipGetLastError();
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_rollout_coop, coop_lds_bytes(L, C));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rollout_coop, dim3(S * A), dim3(TEAM), coop_lds_bytes(L, C), st, m, L, C, X, S, A, P, nominal,
-                     out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied, passive, cost, cost_cand, ch);
-  return hipGetLastError();
+  if (sch) return launch_rollout_sch(m, L, C, X, a, lim);
+  if (use_dual()) return lim ? launch_rollout2<true>(m, L, C, X, a) : launch_rollout2<false>(m, L, C, X, a);
+  // ILQG_DUAL=0: the one-wave kernels
+  const unsigned blocks = a.S * a.A;
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        e = launch(k_rollout_s<decltype(sm), decltype(sx)>, blocks, TEAM, rollout_lds(coop_lds_bytes(L, C)), a.st, m,
+                   a.S, a.A, a.P, a.nominal, a.out, a.out_is_cand, a.K, a.k, a.alphas, a.dinit, a.qfrc_applied,
+                   a.xfrc_applied, a.passive, a.cost, a.cost_cand, a.ch);
+      }))
+    return e;
+  return launch(k_rollout_coop, blocks, TEAM, coop_lds_bytes(L, C), a.st, m, L, C, X, a.S, a.A, a.P, a.nominal, a.out,
+                a.out_is_cand, a.K, a.k, a.alphas, a.dinit, a.qfrc_applied, a.xfrc_applied, a.passive, a.cost,
+                a.cost_cand, a.ch);
 }
 
 bool rollout_clamp_supported() { return use_dual(); }
@@ -344,85 +190,34 @@ hipError_t launch_step_coop(const DevModel& m, const WsLayout& L, const CoopLayo
                             TrajDev stt, int n, int nstep, const double* qfrc_applied, const double* xfrc_applied,
                             hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipError_t e;
-#define ILQG_CASE(id, SMT, SXT)                                                                                  \
-  case id: {                                                                                                     \
-    const size_t lds = coop_lds_bytes(make_layout(stat::SMT{}, stat::SXT::npair), C);                           \
-    e = allow_lds(k_step_s<stat::SMT, stat::SXT>, lds);                                                          \
-    if (e != hipSuccess) return e;                                                                               \
-    hipLaunchKernelGGL((k_step_s<stat::SMT, stat::SXT>), dim3(n), dim3(TEAM), lds, st, m, stt, nstep,           \
-                       qfrc_applied, xfrc_applied);                                                              \
-    return hipGetLastError();                                                                                    \
-  }
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_step_coop, coop_lds_bytes(L, C));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_step_coop, dim3(n), dim3(TEAM), coop_lds_bytes(L, C), st, m, L, C, X, stt, nstep,
-                     qfrc_applied, xfrc_applied);
-  return hipGetLastError();
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        const size_t lds = coop_lds_bytes(make_layout(sm, decltype(sx)::npair), C);
+        e = launch(k_step_s<decltype(sm), decltype(sx)>, n, TEAM, lds, st, m, stt, nstep, qfrc_applied, xfrc_applied);
+      }))
+    return e;
+  return launch(k_step_coop, n, TEAM, coop_lds_bytes(L, C), st, m, L, C, X, stt, nstep, qfrc_applied, xfrc_applied);
 }
 
 hipError_t launch_forward_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                TrajDev stt, int n, const double* qfrc_applied, const double* xfrc_applied,
                                double* qacc, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipError_t e;
-#define ILQG_CASE(id, SMT, SXT)                                                                                  \
-  case id: {                                                                                                     \
-    const size_t lds = coop_lds_bytes(make_layout(stat::SMT{}, stat::SXT::npair), C);                           \
-    e = allow_lds(k_fwd_s<stat::SMT, stat::SXT>, lds);                                                           \
-    if (e != hipSuccess) return e;                                                                               \
-    hipLaunchKernelGGL((k_fwd_s<stat::SMT, stat::SXT>), dim3(n), dim3(TEAM), lds, st, m, stt, qfrc_applied,     \
-                       xfrc_applied, qacc);                                                                      \
-    return hipGetLastError();                                                                                    \
-  }
-  switch (m.static_id) {
-    ILQG_STATIC_MODELS(ILQG_CASE)
-    default:
-      break;
-  }
-#undef ILQG_CASE
-  e = allow_lds(k_fwd_coop, coop_lds_bytes(L, C));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_fwd_coop, dim3(n), dim3(TEAM), coop_lds_bytes(L, C), st, m, L, C, X, stt, qfrc_applied,
-                     xfrc_applied, qacc);
-  return hipGetLastError();
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        const size_t lds = coop_lds_bytes(make_layout(sm, decltype(sx)::npair), C);
+        e = launch(k_fwd_s<decltype(sm), decltype(sx)>, n, TEAM, lds, st, m, stt, qfrc_applied, xfrc_applied, qacc);
+      }))
+    return e;
+  return launch(k_fwd_coop, n, TEAM, coop_lds_bytes(L, C), st, m, L, C, X, stt, qfrc_applied, xfrc_applied, qacc);
 }
 
 }  // namespace ilqg
 
 #ifdef ILQG_STAMPS
-// the rollout kernels' line-search counters (dcoop_impl.h g_ls)
-extern "C" int ilqg_debug_ls_rollout(unsigned long long* out5, int reset) {
-  if (hipMemcpyFromSymbol(out5, HIP_SYMBOL(ilqg::coop::g_ls), sizeof(unsigned long long) * 8) != hipSuccess) return 3;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_ls), z, sizeof(z));
-  }
-  return 0;
-}
+// the rollout kernels' copy of the line-search and stamp counters (coop_common.h)
+extern "C" int ilqg_debug_ls_rollout(unsigned long long* out5, int reset) { return ilqg::debug_ls(out5, reset); }
 extern "C" int ilqg_debug_stamps(unsigned long long* acc, unsigned long long* cnt, int reset) {
-  if (hipMemcpyFromSymbol(acc, HIP_SYMBOL(ilqg::coop::g_stamp_acc), sizeof(unsigned long long) * STAMP_NG) != hipSuccess)
-    return 3;
-  if (hipMemcpyFromSymbol(cnt, HIP_SYMBOL(ilqg::coop::g_stamp_cnt), sizeof(unsigned long long) * STAMP_NG) != hipSuccess)
-    return 3;
-  unsigned long long nw[2];
-  (void)hipMemcpyFromSymbol(&nw[0], HIP_SYMBOL(ilqg::coop::g_newton_iters), 8);
-  (void)hipMemcpyFromSymbol(&nw[1], HIP_SYMBOL(ilqg::coop::g_newton_calls), 8);
-  acc[44] = nw[0];
-  acc[45] = nw[1];
-  if (reset) {
-    unsigned long long z[STAMP_NG] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_newton_iters), z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_newton_calls), z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_stamp_acc), z, sizeof(z));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coop::g_stamp_cnt), z, sizeof(z));
-  }
-  return 0;
+  return ilqg::debug_stamps(acc, cnt, reset);
 }
 #endif

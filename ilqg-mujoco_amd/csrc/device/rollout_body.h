@@ -1,5 +1,6 @@
-// The rollout of one (seed, alpha) candidate (inc/ilqr.h:116-130), shared by the
-// rollout kernels' two translation units: kernels_rollout.hip and, for the
+// The rollout of one (seed, alpha) candidate (inc/ilqr.h:116-130), the default
+// kernels around it and their launcher, shared by the rollout kernels' two
+// translation units: kernels_rollout.hip and, for the
 // cost-schedule variants, kernels_rollout_sch.hip (every instance inlines the
 // whole physics step: one unit would take twice as long to compile).
 #pragma once
@@ -25,38 +26,20 @@
 
 namespace ilqg {
 
-// launch_rollout_coop's arguments, as handed on to the cost-schedule launchers
-struct RollArgs {
-  int S, A, P;
-  TrajDev nominal, out;
-  int out_is_cand;
-  const double *K, *k, *alphas;
-  TrajDev dinit;
-  const double *qfrc_applied, *xfrc_applied;
-  int passive;
-  CostDev cost;
-  double* cost_cand;
-  hipStream_t st;
-  RollChunk ch;
-  int cstride;
-};
-// kernels_rollout_sch.hip: the scheduled variants of k_rollout2_s (done = the
-// model has a compiled specialisation and the launch was made) and of
-// k_rollout2_coop (lds_d, ch.dbuf, nv27 as launch_rollout_coop chose them)
-hipError_t launch_rollout_sch_static(const DevModel& m, const coop::CoopLayout& C, const RollArgs& a, bool lim,
-                                     bool& done);
-hipError_t launch_rollout_sch_generic(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                                      const coop::CoopAux& X, const RollArgs& a, bool lim, bool nv27, size_t lds_d);
+// kernels_rollout_sch.hip: launch_rollout_coop's launch while a cost schedule
+// is set (a.cstride != 0), clamped to the control limits or not
+hipError_t launch_rollout_sch(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
+                              const coop::CoopAux& X, const RollArgs& a, bool lim);
 
 namespace {
 
 __device__ inline void rollout_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
                                 int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, int wave, auto split, auto lowreg, auto clamp, auto sched, int cstride = 0) {
-  // clamp (the *_lim kernels, launched while control limits are set): the
-  // control law's output confined to [ch.ulim[i], ch.ulim[nu + i]]
-  // sched (the *_sch kernels, launched while a cost schedule is set): point n
-  // is charged with row n of the schedule, cost.wq + n cstride, which is
-  // packed as stage_cost lays the LDS copy out (wq tq lq wv tv lv wu tu lu)
+  // clamp (the kernels' LIM instances, launched while control limits are set):
+  // the control law's output confined to [ch.ulim[i], ch.ulim[nu + i]]
+  // sched (their <.., int> instances, launched while a cost schedule is set):
+  // point n is charged with row n of the schedule, cost.wq + n cstride, which
+  // is packed as stage_cost lays the LDS copy out (wq tq lq wv tv lv wu tu lu)
   // wave < 0: one-wave team; 0/1: primary/helper wave of a two-wave team (step_dual)
   const bool prim = wave <= 0;
   STAMP_INIT();
@@ -319,6 +302,79 @@ inline size_t rollout_lds(size_t need) {
     pad = e ? atol(e) : 0;
   }
   return (size_t)pad > need ? (size_t)pad : need;
+}
+
+// ---- the default rollout kernels.  LIM: the control law clamped to the
+// solver's control limits (RollChunk.ulim); SCH...: a cost schedule's row
+// stride (coop_common.h).  Each unit instantiates the ones it launches.
+// two-wave teams (step_dual): 128 threads per (seed, candidate).  MT: DevModel,
+// or DevModelNV<27> for 27-dof models (the humanoid: compile-time sizes in the
+// Newton Cholesky and its substitution)
+template <class MT, bool LIM, class... SCH>
+__global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, SCH... cstride) {
+  Team T = make_team(L, C);
+  MT m;
+  CoopAux X;
+  stage_model(mg, Xg, L, C, T, m, X);
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
+               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
+               std::bool_constant<LIM>{}, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+}
+// three-wave teams for the compile-time register-row models (rollout_waves)
+template <class SM, class SX, bool LIM, class... SCH>
+__global__ __launch_bounds__(3 * TEAM) void k_rollout2_s(DevModel mg, int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, SCH... cstride) {
+  static constexpr WsLayout L = make_layout(SM{}, SX::npair, true);
+  static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
+  static constexpr SX X{};
+  Team T = make_team(L, C);
+  SM m;
+  stage_model_sep(mg, T, m);
+  rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
+               passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
+               std::false_type{}, std::bool_constant<LIM>{}, std::bool_constant<(sizeof...(SCH) > 0)>{},
+               sched_stride(cstride...));
+}
+
+// the second buffer of the generic kernel's record, past the workspace when it
+// fits (RollChunk.dbuf; ILQG_ROLL_DBUF=0 keeps the register prefetch, A/B):
+// sets ch.dbuf and returns the launch's LDS
+inline size_t rollout_dbuf_lds(const DevModel& m, const WsLayout& L, const CoopLayout& C, size_t lds, RollChunk& ch) {
+  static const int dbuf_env = [] {
+    const char* v = getenv("ILQG_ROLL_DBUF");
+    return (v && v[0] == '0') ? 0 : 1;
+  }();
+  const size_t R = (size_t)m.nq + m.nv + m.nu + (size_t)m.nu * 2 * m.nv + m.nu;
+  const size_t need = (coop_lds_bytes(L, C) + 15) / 16 * 16 + R * sizeof(double);
+  if (dbuf_env && need <= 160 * 1024) {
+    ch.dbuf = 1;
+    return need > lds ? need : lds;
+  }
+  return lds;
+}
+
+// launch of the default kernels: the bundled model's k_rollout2_s, or
+// k_rollout2_coop; cs... is the cost schedule's stride (SCH = int) or empty
+template <bool LIM, class... SCH>
+hipError_t launch_rollout2(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
+                           const RollArgs& a, SCH... cs) {
+  const unsigned blocks = a.S * a.A;
+  hipError_t e = hipSuccess;
+  if (for_static_model(m.static_id, [&](auto sm, auto sx) {
+        using SM = decltype(sm);
+        using SX = decltype(sx);
+        const size_t lds2 = rollout_lds(coop_lds_bytes(make_layout(sm, SX::npair, true), C));
+        e = launch(k_rollout2_s<SM, SX, LIM, SCH...>, blocks, rollout_waves<SM>() * TEAM, lds2, a.st, m, a.S, a.A, a.P,
+                   a.nominal, a.out, a.out_is_cand, a.K, a.k, a.alphas, a.dinit, a.qfrc_applied, a.xfrc_applied,
+                   a.passive, a.cost, a.cost_cand, a.ch, cs...);
+      }))
+    return e;
+  RollChunk ch = a.ch;
+  const size_t lds_d = rollout_dbuf_lds(m, L, C, rollout_lds(coop_lds_bytes(L, C)), ch);
+  return for_model_type<DevModelNV>(m, [&](auto mt) {
+    return launch(k_rollout2_coop<typename decltype(mt)::type, LIM, SCH...>, blocks, 2 * TEAM, lds_d, a.st, m, L, C, X,
+                  a.S, a.A, a.P, a.nominal, a.out, a.out_is_cand, a.K, a.k, a.alphas, a.dinit, a.qfrc_applied,
+                  a.xfrc_applied, a.passive, a.cost, a.cost_cand, ch, cs...);
+  });
 }
 
 }  // namespace

@@ -624,7 +624,7 @@ def test_clamp_under_a_clipping_model(ia):
 @gpu
 @pytest.mark.parametrize("name", ("chain", "humanoid"))
 def test_generic_rollout_clamps(ia, ora, name):
-    """the clamped variants of the generic rollout kernel (k_rollout2_coop_lim:
+    """the clamped variants of the generic rollout kernel (k_rollout2_coop<MT, true>:
     the run-time instance for the chain, the 27-dof one for the humanoid), H = 5.
     With K = 0 the control law is alpha k + u* whatever the state, so the
     limited run's ctrl is exactly the clip of the unlimited run's.  The chain's
