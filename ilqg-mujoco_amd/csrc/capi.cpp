@@ -322,6 +322,13 @@ struct ilqg_solver {
   bool limits = false, cl_valid = false;
   std::vector<double> host_lim;
   DevBuf ulim, cl_mask, cl_info;
+  // recursion mode (ilqg_solver_set_recursion): STANDARD routes ilqg_backward to
+  // launch_backward_std, whose per-seed expected reduction and first fallback
+  // step land in ex_dV / ex_bad; ex_valid: the last backward pass was a standard
+  // one (ilqg_solver_get_expected reads 0 / -1 otherwise)
+  int recursion = ILQG_RECURSION_REFERENCE;
+  bool ex_valid = false;
+  DevBuf ex_dV, ex_bad;
   // cost schedule (ilqg_solver_set_cost_schedule): one packed cost row per
   // trajectory point, [P][csz], shared by every seed; sched[sched_cur] is the
   // table in force and the other buffer the target of the next shift (a shift
@@ -330,7 +337,7 @@ struct ilqg_solver {
   int sched_cur = 0, csz = 0;
   DevBuf sched[2];
   std::vector<double> host_cost;
-  // the fused sweep streams the bit-exact, unboxed recursion behind the fp64 sweep
+  // the fused sweep streams the bit-exact, unboxed reference recursion behind the fp64 sweep
   void choose_fused();
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[ILQG_NKERNEL];
@@ -422,7 +429,7 @@ struct ilqg_solver {
 
 static bool fused_ok(const ilqg_model* m);
 void ilqg_solver::choose_fused() {
-  fused = !limits && riccati == ILQG_RICCATI_EXACT && fdprec == ILQG_FD_F64 && fused_ok(model) && sync.p;
+  fused = !limits && recursion == ILQG_RECURSION_REFERENCE && riccati == ILQG_RICCATI_EXACT && fdprec == ILQG_FD_F64 && fused_ok(model) && sync.p;
 }
 
 static std::vector<double> pack_cost(const HostModel& m, const ilqg_cost* c) {
@@ -1344,7 +1351,14 @@ int ilqg_backward(ilqg_solver* s) {
   s->grp_join = true;
   const ilqg_model* m = s->model;
   s->cl_valid = s->limits;
+  s->ex_valid = s->recursion == ILQG_RECURSION_STANDARD;
   HIPCHK(s->timed(4, [&] {
+    // the standard recursion (set_recursion keeps limits and the MFMA engine out)
+    if (s->recursion == ILQG_RECURSION_STANDARD)
+      return launch_backward_std(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
+                                 s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
+                                 s->flags(), StdDev{s->cview(), s->cstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
+                                 s->stream);
     // control limits: the boxed recursion (set_ctrl_limits keeps the MFMA engine out)
     if (s->limits)
       return launch_backward_box(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
@@ -1398,6 +1412,7 @@ static int iterate_groups(ilqg_solver* s) {
     HIPCHK(hipStreamWaitEvent(r.st, s->grp_sel[g], 0));
     // the sweep with the group's recursion streamed behind it: one launch
     s->cl_valid = false;
+    s->ex_valid = false;
     HIPCHK(s->timed(5, [&] { return fused_launch(s, r, 1); }, r.st));
     HIPCHK(hipEventRecord(s->grp_done[g], r.st));
   }
@@ -1416,6 +1431,7 @@ int ilqg_iterate(ilqg_solver* s) {
   if (s->fused) {
     // FD sweep with the Riccati recursion of every seed streamed behind it (one launch)
     s->cl_valid = false;
+    s->ex_valid = false;
     HIPCHK(s->timed(5, [&] { return fused_launch(s, whole(s), 1); }));
     s->vinit_pending = false;
     return ILQG_OK;
@@ -1529,6 +1545,9 @@ int ilqg_solver_set_ctrl_limits(ilqg_solver* s, const double* lo, const double* 
   if (s->ngroups > 1)
     return fail(ILQG_ERR_UNSUPPORTED, "control limits: seed groups stream the unboxed recursion "
                                       "(ilqg_solver_set_groups(s, 1) first)");
+  if (s->recursion == ILQG_RECURSION_STANDARD)
+    return fail(ILQG_ERR_UNSUPPORTED, "control limits: the standard recursion has no boxed variant "
+                                      "(ilqg_solver_set_recursion(s, ILQG_RECURSION_REFERENCE) first)");
   if (backward_box_lds_bytes(h.nv, h.nu) > kMaxLds)
     return fail(ILQG_ERR_UNSUPPORTED, "control limits: the boxed Riccati workspace exceeds one CU's 160 KB of LDS");
   HIPCHK(s->sync_all());  // launches already enqueued keep the limits they were given
@@ -1542,6 +1561,53 @@ int ilqg_solver_set_ctrl_limits(ilqg_solver* s, const double* lo, const double* 
   HIPCHK(hipMemcpy(s->ulim.p, s->host_lim.data(), 2 * nu * 8, hipMemcpyHostToDevice));
   s->limits = true;
   s->fused = false;  // rollout, select, sweep, then the boxed ilqg_backward
+  return ILQG_OK;
+}
+
+int ilqg_solver_set_recursion(ilqg_solver* s, int mode) {
+  if (!s || (mode != ILQG_RECURSION_REFERENCE && mode != ILQG_RECURSION_STANDARD))
+    return fail(ILQG_ERR_ARG, "bad argument");
+  const HostModel& h = s->model->host;
+  if (mode == ILQG_RECURSION_STANDARD) {
+    if (h.nq != h.nv)
+      return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: nq != nv (the tangent-space Hessian of a quaternion "
+                                        "term is not diagonal)");
+    if (s->riccati == ILQG_RICCATI_MFMA)
+      return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: the MFMA Riccati engine has no standard variant "
+                                        "(ilqg_solver_set_riccati(s, ILQG_RICCATI_EXACT) first)");
+    if (s->limits)
+      return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: no boxed variant; switch the control limits off first "
+                                        "(ilqg_solver_set_ctrl_limits(s, NULL, NULL))");
+    if (s->ngroups > 1)
+      return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: seed groups stream the reference recursion "
+                                        "(ilqg_solver_set_groups(s, 1) first)");
+    if (h.nu > 32 || backward_std_lds_bytes(h.nv, h.nu) > kMaxLds)
+      return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: the Riccati workspace exceeds one CU's 160 KB of LDS");
+  }
+  HIPCHK(s->sync_all());  // launches already enqueued keep the mode they were given
+  if (mode == ILQG_RECURSION_STANDARD && !s->ex_dV.p) {
+    HIPCHK(s->ex_dV.alloc((size_t)s->S * 2 * sizeof(double)));
+    HIPCHK(s->ex_bad.alloc((size_t)s->S * sizeof(int)));
+  }
+  s->recursion = mode;
+  // STANDARD: rollout, select, sweep, then ilqg_backward; REFERENCE: the solver as created
+  s->choose_fused();
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_expected(ilqg_solver* s, double* dV, int* first_bad) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  HIPCHK(s->sync_all());
+  const size_t S = (size_t)s->S;
+  const bool have = s->ex_valid && s->ex_dV.p;
+  if (dV) {
+    if (have) HIPCHK(hipMemcpy(dV, s->ex_dV.p, S * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    else std::fill(dV, dV + 2 * S, 0.0);
+  }
+  if (first_bad) {
+    if (have) HIPCHK(hipMemcpy(first_bad, s->ex_bad.p, S * sizeof(int), hipMemcpyDeviceToHost));
+    else std::fill(first_bad, first_bad + S, -1);
+  }
   return ILQG_OK;
 }
 
@@ -1670,6 +1736,9 @@ int ilqg_solver_set_riccati(ilqg_solver* s, int mode) {
     if (s->limits)
       return fail(ILQG_ERR_UNSUPPORTED, "MFMA Riccati: no boxed variant; switch the control limits off first "
                                         "(ilqg_solver_set_ctrl_limits(s, NULL, NULL))");
+    if (s->recursion == ILQG_RECURSION_STANDARD)
+      return fail(ILQG_ERR_UNSUPPORTED, "MFMA Riccati: the standard recursion runs on the exact engine only "
+                                        "(ilqg_solver_set_recursion(s, ILQG_RECURSION_REFERENCE) first)");
   }
   HIPCHK(s->sync_all());
   s->riccati = mode;
@@ -1712,6 +1781,9 @@ int ilqg_solver_set_groups(ilqg_solver* s, int ngroups) {
   if (ngroups > 1 && s->limits)
     return fail(ILQG_ERR_UNSUPPORTED, "seed groups stream the unboxed recursion; switch the control limits off first "
                                       "(ilqg_solver_set_ctrl_limits(s, NULL, NULL))");
+  if (ngroups > 1 && s->recursion == ILQG_RECURSION_STANDARD)
+    return fail(ILQG_ERR_UNSUPPORTED, "seed groups stream the reference recursion; "
+                                      "ilqg_solver_set_recursion(s, ILQG_RECURSION_REFERENCE) first");
   HIPCHK(s->sync_all());
   s->free_groups();
   s->grp_join = true;

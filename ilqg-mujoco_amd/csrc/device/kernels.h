@@ -99,7 +99,22 @@ struct BoxDev {
 hipError_t launch_backward_box(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
                                double* K, double* k, double* V, double* v, RicFlags fl, BoxDev bx, hipStream_t st);
 size_t backward_box_lds_bytes(int nv, int nu);
-// the same recursion with the matrix products on the fp64 matrix cores
+// the standard recursion (ilqg_solver_set_recursion; riccati.h backward_seed
+// with STD): exact diagonal cost Hessians from the cost row of each step's
+// point (cost_at(cost, n, cstride)), mu in Quu / Qux only, no c term.  dV:
+// [S][2], the expected reduction's linear and quadratic terms; bad: [S], the
+// first step that took the indefinite-step fallback (K = 0, k = 0), or -1.
+// Models with nq == nv only (the caller checks).
+struct StdDev {
+  CostDev cost{};
+  int cstride = 0;
+  double* dV = nullptr;
+  int* bad = nullptr;
+};
+hipError_t launch_backward_std(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
+                               double* K, double* k, double* V, double* v, RicFlags fl, StdDev sd, hipStream_t st);
+size_t backward_std_lds_bytes(int nv, int nu);
+// the reference recursion with the matrix products on the fp64 matrix cores
 // (riccati_mfma.h): one 8-wave workgroup per seed; agrees with the oracle to
 // rounding (the product sums run in the matrix core's order)
 hipError_t launch_backward_mfma(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,

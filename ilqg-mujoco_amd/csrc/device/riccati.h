@@ -687,15 +687,34 @@ __device__ inline int box_solve(int nu, const BoxLds& L, double* Mm, const doubl
   return box_uni(state) == 1 ? iters : -1;
 }
 
-template <int NV_, int NU_, bool BOX = false, class MD>
+// ---- the standard step (STD instances of backward_seed, ILQG_RECURSION_STANDARD;
+// it replaces inc/ilqr.h:157-174, whose outer-product Hessians, resident mu and
+// factors of 2 it does not keep).  Deviation coordinates about the nominal
+// trajectory (no c term), the exact diagonal Hessians of ilqg_cost from the
+// cost row of the step's point, mu in Quu and Qux only (Tassa, Erez & Todorov
+// 2012, eq. 10), and the value update in its closed-loop form, which holds for
+// any gains:
+//   Quu_r = luu + B'(V + mu I)B   Qux_r = B'(V + mu I)A   Qu = r + B'v
+//   k = -Quu_r^-1 Qu              K = -Quu_r^-1 Qux_r
+//   dV1 += k'Qu                   dV2 += 1/2 k'(luu + B'VB)k
+//   V <- lxx + K'luu K + (A+BK)'V(A+BK)
+//   v <- q + K'(r + luu k) + (A+BK)'(v + V B k)
+// A step whose Quu_r has a pivot <= 0 or NaN (or whose gains come out
+// non-finite) takes K = 0, k = 0 and adds nothing to dV (the decision is
+// wave-uniform, box_uni).
+// extra LDS of an STD instance, in doubles: the unregularised Quu, lxx, luu
+__host__ __device__ constexpr size_t std_lds_doubles(size_t nv, size_t nu) { return nu * nu + 2 * nv + nu; }
+
+template <int NV_, int NU_, bool BOX = false, bool STD = false, class MD>
 __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, int P, double dt, double mu,
                                      const double* deriv, int Ds, TrajDev tr, double* Kg, double* kg, double* Vg,
                                      double* vg, int s, int tid, double* sh, const unsigned* done, unsigned target,
-                                     unsigned* fault, RicFlags fl, BoxDev bx = BoxDev{}) {
+                                     unsigned* fault, RicFlags fl, BoxDev bx = BoxDev{}, StdDev sd = StdDev{}) {
+  static_assert(!(BOX && STD), "the boxed step is the reference recursion's");
 #ifndef ILQG_RIC_LDS
   // bundled small models: the register/exchange formulation (riccati_reg.h)
-  // (a BOX instance is always the LDS formulation below)
-  if constexpr (!BOX && RicReg<NV_, NU_>::ok) {
+  // (a BOX or STD instance is always the LDS formulation below)
+  if constexpr (!BOX && !STD && RicReg<NV_, NU_>::ok) {
     if (nq == NV_) {
       backward_seed_reg<NV_, NU_>(m, P, dt, mu, deriv, Ds, tr, Kg, kg, Vg, vg, s, tid, sh, done, target, fault, fl);
       return;
@@ -766,6 +785,25 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     bL.gc = bL.xc + nu;
     dl = bL.gc + nu;  // box_lds_doubles(nu) further on
   }
+  // STD: Qo = luu + B'VB (Mm holds the regularised one, factored in place);
+  // lxx, luu: the diagonals 2 (wq, wv), 2 wu of the step's cost row
+  double *Qo = nullptr, *lxx = nullptr, *luu = nullptr;
+  if constexpr (STD) {
+    Qo = dl;
+    lxx = Qo + nu * nu;
+    luu = lxx + nx;
+    dl = luu + nu;  // std_lds_doubles(nv, nu) further on
+  }
+  // STD: lxx, luu of point p's cost row
+  auto hess = [&](int p) {
+    if constexpr (STD) {
+      const CostDev cr = cost_at(sd.cost, p, sd.cstride);
+      for (int i = tid; i < nx; i += BW_THREADS) lxx[i] = 2 * (i < nv ? cr.wq[i] : cr.wv[i - nv]);
+      for (int a = tid; a < nu; a += BW_THREADS) luu[a] = 2 * cr.wu[a];
+    }
+  };
+  double dV1 = 0, dV2 = 0;  // STD: the expected reduction's two terms, the same in every lane
+  int first_bad = -1;       // STD: the first step that took the fallback
   int* trn = (int*)(dl + (pref ? D : 0));
   double* T4 = A;
   double* Vn = V;
@@ -783,10 +821,12 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     const double* d1 = deriv + ((size_t)s * P + (P > 1 ? 1 : 0)) * Ds;
     if (pref)
       for (int i = tid; i < D; i += BW_THREADS) dl[i] = ld(d1 + rec_src(i, nv, nu, fl.layout));
+    hess(0);
     __syncthreads();
     for (int e = tid; e < nx * nx; e += BW_THREADS) {
       int i = e % nx, j = e / nx;
-      V[i + j * LX] = fl.vinit ? Vg[(size_t)s * nx * nx + e] : v[i] * v[j];
+      if constexpr (STD) V[i + j * LX] = fl.vinit ? Vg[(size_t)s * nx * nx + e] : (i == j ? lxx[i] : 0.0);
+      else V[i + j * LX] = fl.vinit ? Vg[(size_t)s * nx * nx + e] : v[i] * v[j];
     }
     __syncthreads();
   }
@@ -794,7 +834,7 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
   // the nominal states for c = x*_{n-1} - x*_n: one lane per component, in
   // registers, each point loaded one step ahead (nq == nv; quaternion models
   // take the tangent-space difference from memory below)
-  const bool xreg = nq == nv && nx <= BW_THREADS;
+  const bool xreg = !STD && nq == nv && nx <= BW_THREADS;
   auto xload = [&](size_t pt) -> double {
     return tid < nv ? tr.qpos[pt * nq + tid] : (tid < nx ? tr.qvel[pt * nv + tid - nv] : 0.0);
   };
@@ -840,7 +880,9 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     for (int i = tid; i < nx; i += BW_THREADS) {
       q[i] = dn(2 * nv * nv + nv * nu + i);
       // c = x*_{n-1} (-) x*_n (inc/ilqr.h:154-157; tangent space for quaternion joints)
-      if (xreg) {
+      if constexpr (STD) {
+        // deviation coordinates: no c
+      } else if (xreg) {
         c[i] = xa - xb;  // i == tid
       } else if (i < nv && nq != nv) {
         c[i] = dev::state_diff_dof(m, i, tr.qpos + pp * nq, tr.qpos + pc * nq);
@@ -859,11 +901,37 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
         bL.bh[a] = bx.hi[a] - us;
       }
     }
+    hess(n);  // (the step before ended on a barrier behind its last read of lxx, luu)
     __syncthreads();
-    for (int i = tid; i < nx; i += BW_THREADS) Vs[i + i * LX] += mu;
-    __syncthreads();
+    if constexpr (!STD) {
+      for (int i = tid; i < nx; i += BW_THREADS) Vs[i + i * LX] += mu;
+      __syncthreads();
+    }
     BSTAMP(0);
     // stage 2: T1 = B'V
+    if constexpr (STD) {
+      // T1 = B'(V + mu I), the diagonal term added inside the sum; T6 (free
+      // until stage 5) takes the unregularised B'V, ld nu
+      double* T1u = T6;
+      ILP3_BEGIN(nu * nx)
+        double s0 = 0, s1 = 0, s2 = 0, u0 = 0, u1 = 0, u2 = 0;
+        const int a0 = e0 % nu, j0 = e0 / nu, a1 = f1 % nu, j1 = f1 / nu, a2 = f2 % nu, j2 = f2 / nu;
+        for (int kk = 0; kk < nx; kk++) {
+          const double b0 = B[kk + a0 * LX], b1 = B[kk + a1 * LX], b2 = B[kk + a2 * LX];
+          const double v0 = Vs[kk + j0 * LX], v1 = Vs[kk + j1 * LX], v2 = Vs[kk + j2 * LX];
+          u0 += b0 * v0;
+          u1 += b1 * v1;
+          u2 += b2 * v2;
+          s0 += b0 * (kk == j0 ? v0 + mu : v0);
+          s1 += b1 * (kk == j1 ? v1 + mu : v1);
+          s2 += b2 * (kk == j2 ? v2 + mu : v2);
+        }
+        T1[e0] = s0;
+        T1u[e0] = u0;
+        if (h1) T1[e1] = s1, T1u[e1] = u1;
+        if (h2) T1[e2] = s2, T1u[e2] = u2;
+      }
+    } else {
     ILP3_BEGIN(nu * nx)
       double s0 = 0, s1 = 0, s2 = 0;
       const int a0 = e0 % nu, j0 = e0 / nu, a1 = f1 % nu, j1 = f1 / nu, a2 = f2 % nu, j2 = f2 / nu;
@@ -876,14 +944,24 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       if (h1) T1[e1] = s1;
       if (h2) T1[e2] = s2;
     }
+    }
     __syncthreads();
     BSTAMP(1);
     // stage 3: Mm = -2 T1 B - 2R ; T3 = T1 A ; w = v + 2 V c
+    // (STD: Mm = luu + T1 B = Quu_r, Qo = luu + T1u B = Quu ; T3 = Qux_r ; w = v)
     for (int e = tid; e < nu * nu; e += BW_THREADS) {
       int a = e % nu, b = e / nu;
       double sm = 0;
       for (int kk = 0; kk < nx; kk++) sm += T1[a + kk * nu] * B[kk + b * LX];
-      Mm[e] = -2 * sm - 2 * (r[a] * r[b]);
+      if constexpr (STD) {
+        double su = 0;
+        for (int kk = 0; kk < nx; kk++) su += T6[a + kk * nu] * B[kk + b * LX];
+        const double l = a == b ? luu[a] : 0.0;
+        Mm[e] = l + sm;
+        Qo[e] = l + su;
+      } else {
+        Mm[e] = -2 * sm - 2 * (r[a] * r[b]);
+      }
       if constexpr (BOX) bL.Mo[e] = Mm[e];
     }
     ILP3_BEGIN(nu * nx)
@@ -899,9 +977,13 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       if (h2) T3[e2] = s2;
     }
     for (int i = tid; i < nx; i += BW_THREADS) {
-      double sm = 0;
-      for (int j = 0; j < nx; j++) sm += Vs[i + j * LX] * c[j];
-      w[i] = v[i] + 2 * sm;
+      if constexpr (STD) {
+        w[i] = v[i];
+      } else {
+        double sm = 0;
+        for (int j = 0; j < nx; j++) sm += Vs[i + j * LX] * c[j];
+        w[i] = v[i] + 2 * sm;
+      }
     }
     __syncthreads();
     ldlt_factor_wave(nu, Mm, trn, y, tid);  // y is free until stage 5
@@ -918,9 +1000,9 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     for (int j = tid; j < nx + 1; j += BW_THREADS) {
       double* x = j < nx ? Kl + j * nu : kl;
       if (j < nx)
-        for (int a = 0; a < nu; a++) x[a] = 2 * T3[a + j * nu];
+        for (int a = 0; a < nu; a++) x[a] = STD ? -T3[a + j * nu] : 2 * T3[a + j * nu];
       else
-        for (int a = 0; a < nu; a++) x[a] = col[a];
+        for (int a = 0; a < nu; a++) x[a] = STD ? -col[a] : col[a];
     }
     __syncthreads();
     if (nu <= 32 && nx + 1 <= BW_THREADS) {
@@ -980,7 +1062,36 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
         bx.info[pc] = cinfo;
       }
     }
+    if constexpr (STD) {
+      // Quu_r must be positive definite: every pivot of the factor positive (a
+      // NaN fails the comparison).  Otherwise the uncontrolled step.
+      int ok = 1;
+      for (int a = 0; a < nu; a++) ok &= Mm[a + a * nu] > 0 ? 1 : 0;
+      // (and gains that overflowed, from finite records of absurd size, count as indefinite)
+      int fin = 1;
+      for (int e = tid; e < nu * nx; e += BW_THREADS) fin &= fabs(Kl[e]) <= 1.7976931348623157e308 ? 1 : 0;
+      if (tid < nu) fin &= fabs(kl[tid]) <= 1.7976931348623157e308 ? 1 : 0;
+      ok &= __ballot(!fin) == 0ull ? 1 : 0;
+      if (box_uni(!ok)) {
+        if (first_bad < 0) first_bad = n;
+        for (int e = tid; e < nu * nx; e += BW_THREADS) Kl[e] = 0.0;
+        if (tid < nu) kl[tid] = 0.0;
+        __syncthreads();
+      } else {
+        // every lane the same sums from the same LDS values: col = Qu
+        double d1 = 0, d2 = 0;
+        for (int a = 0; a < nu; a++) {
+          double sm = 0;
+          for (int b = 0; b < nu; b++) sm += Qo[a + b * nu] * kl[b];
+          d1 += kl[a] * col[a];
+          d2 += kl[a] * sm;
+        }
+        dV1 += d1;
+        dV2 += 0.5 * d2;
+      }
+    }
     // stage 5: ABK = A + B K ; T6 = K'R ; y = Bk + c ; kR = k'R
+    // (STD: T6 = K'luu ; y = Bk ; kR = r + luu k)
     for (int e = tid; e < nx * nx; e += BW_THREADS) {
       int i = e % nx, j = e / nx;
       double sm = 0;
@@ -989,19 +1100,28 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     }
     for (int e = tid; e < nx * nu; e += BW_THREADS) {
       int i = e % nx, b = e / nx;
-      double sm = 0;
-      for (int a = 0; a < nu; a++) sm += Kl[a + i * nu] * (r[a] * r[b]);
-      T6[i + b * LX] = sm;
+      if constexpr (STD) {
+        T6[i + b * LX] = Kl[b + i * nu] * luu[b];
+      } else {
+        double sm = 0;
+        for (int a = 0; a < nu; a++) sm += Kl[a + i * nu] * (r[a] * r[b]);
+        T6[i + b * LX] = sm;
+      }
     }
     for (int i = tid; i < nx; i += BW_THREADS) {
       double sm = 0;
       for (int a = 0; a < nu; a++) sm += B[i + a * LX] * kl[a];
-      y[i] = sm + c[i];
+      if constexpr (STD) y[i] = sm;
+      else y[i] = sm + c[i];
     }
     for (int b = tid; b < nu; b += BW_THREADS) {
-      double sm = 0;
-      for (int a = 0; a < nu; a++) sm += kl[a] * (r[a] * r[b]);
-      kR[b] = sm;
+      if constexpr (STD) {
+        kR[b] = r[b] + luu[b] * kl[b];
+      } else {
+        double sm = 0;
+        for (int a = 0; a < nu; a++) sm += kl[a] * (r[a] * r[b]);
+        kR[b] = sm;
+      }
     }
     __syncthreads();
     BSTAMP(4);
@@ -1034,12 +1154,33 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
         b1s += T6[i1 + b * LX] * Kl[b + j1 * nu];
         b2s += T6[i2 + b * LX] * Kl[b + j2 * nu];
       }
+      if constexpr (STD) {
+        Vn[i0 + j0 * LX] = (a0s + (i0 == j0 ? lxx[i0] : 0.0)) + b0s;
+        if (h1) Vn[i1 + j1 * LX] = (a1s + (i1 == j1 ? lxx[i1] : 0.0)) + b1s;
+        if (h2) Vn[i2 + j2 * LX] = (a2s + (i2 == j2 ? lxx[i2] : 0.0)) + b2s;
+      } else {
       Vn[i0 + j0 * LX] = (a0s + q[i0] * q[j0]) + b0s;
       if (h1) Vn[i1 + j1 * LX] = (a1s + q[i1] * q[j1]) + b1s;
       if (h2) Vn[i2 + j2 * LX] = (a2s + q[i2] * q[j2]) + b2s;
+      }
     }
     __syncthreads();
     BSTAMP(6);
+    if constexpr (STD) {
+      // stage 8: z = v + V (B k) (the OLD V, symmetrised) ; v_new = (q + K'kR) + (A+BK)'z
+      for (int i = tid; i < nx; i += BW_THREADS) {
+        double sm = 0;
+        for (int j = 0; j < nx; j++) sm += Vs[i + j * LX] * y[j];
+        z[i] = v[i] + sm;
+      }
+      __syncthreads();
+      for (int j = tid; j < nx; j += BW_THREADS) {
+        double ta = 0, td = 0;
+        for (int i = 0; i < nx; i++) ta += z[i] * ABK[i + j * LX];
+        for (int b = 0; b < nu; b++) td += kR[b] * Kl[b + j * nu];
+        vn[j] = (q[j] + td) + ta;
+      }
+    } else {
     // stage 8: z = (2y)' V_new ; v_new (reads the NEW V, Q14)
     for (int j = tid; j < nx; j += BW_THREADS) {
       double sm = 0;
@@ -1055,6 +1196,7 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       }
       for (int b = 0; b < nu; b++) td += (2 * kR[b]) * Kl[b + j * nu];
       vn[j] = ((ta + tb) + q[j]) + td;
+    }
     }
     BSTAMP(7);
     // gains out
@@ -1077,10 +1219,18 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
   if (Vg)
     for (int e = tid; e < nx * nx; e += BW_THREADS) {
       int i = e % nx, j = e / nx;
-      Vg[(size_t)s * nx * nx + e] = V[i + j * LX];
+      if constexpr (STD) Vg[(size_t)s * nx * nx + e] = (V[i + j * LX] + V[j + i * LX]) / 2;  // V <- (V + V')/2
+      else Vg[(size_t)s * nx * nx + e] = V[i + j * LX];
     }
   if (vg)
     for (int i = tid; i < nx; i += BW_THREADS) vg[(size_t)s * nx + i] = v[i];
+  if constexpr (STD) {
+    if (tid == 0) {
+      sd.dV[2 * (size_t)s] = dV1;
+      sd.dV[2 * (size_t)s + 1] = dV2;
+      sd.bad[s] = first_bad;
+    }
+  }
 }
 
 

@@ -12,6 +12,7 @@
 
 #include "dphys.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace ilqg {
 namespace {
@@ -75,6 +76,18 @@ __global__ __launch_bounds__(BW_THREADS) void k_backward_box(DevModel m, int nq,
   extern __shared__ double sh[];
   backward_seed<NV_, NU_, true>(m, nq, nv_rt, nu_rt, P, dt, mu, deriv, Ds, tr, Kg, kg, Vg, vg, blockIdx.x, threadIdx.x,
                                 sh, nullptr, 0u, nullptr, fl, bx);
+}
+
+// the standard recursion (StdDev, kernels.h; replaces inc/ilqr.h:157-174):
+// backward_seed's LDS formulation with the STD step; never streamed
+template <int NV_, int NU_>
+__global__ __launch_bounds__(BW_THREADS) void k_backward_std(DevModel m, int nq, int nv_rt, int nu_rt, int P,
+                                                             double dt, double mu, const double* deriv, int Ds,
+                                                             TrajDev tr, double* Kg, double* kg, double* Vg, double* vg,
+                                                             RicFlags fl, StdDev sd) {
+  extern __shared__ double sh[];
+  backward_seed<NV_, NU_, false, true>(m, nq, nv_rt, nu_rt, P, dt, mu, deriv, Ds, tr, Kg, kg, Vg, vg, blockIdx.x,
+                                       threadIdx.x, sh, nullptr, 0u, nullptr, fl, BoxDev{}, sd);
 }
 
 template <int NV, int NU>
@@ -183,6 +196,27 @@ hipError_t launch_backward_box(const DevModel& m, int S, int P, double mu, const
   if (m.nv == 6 && m.nu == 3) return launch_box_t<6, 3>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
   if (m.nv == 2 && m.nu == 1) return launch_box_t<2, 1>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
   return launch_box_t<0, 0>(m, S, P, mu, deriv, Ds, tr, K, k, V, v, fl, bx, lds, st);
+}
+
+// k_backward's workspace, the unregularised Quu and the two Hessian diagonals
+size_t backward_std_lds_bytes(int nv, int nu) {
+  return backward_lds_bytes(nv, nu) + std_lds_doubles((size_t)nv, (size_t)nu) * sizeof(double);
+}
+
+hipError_t launch_backward_std(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
+                               double* K, double* k, double* V, double* v, RicFlags fl, StdDev sd, hipStream_t st) {
+  // lxx = 2 diag(wq, wv) is the Hessian in the tangent space only where nq == nv
+  if (m.nu > 32 || m.nq != m.nv || !sd.cost.wq || !sd.cost.wv || !sd.cost.wu || !sd.dV || !sd.bad)
+    return hipErrorInvalidValue;
+  const size_t lds = backward_std_lds_bytes(m.nv, m.nu);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const auto go = [&](auto kern) {
+    return launch(kern, (unsigned)S, (unsigned)BW_THREADS, lds, st, m, m.nq, m.nv, m.nu, P, m.opt_timestep, mu, deriv,
+                  Ds, tr, K, k, V, v, fl, sd);
+  };
+  if (m.nv == 6 && m.nu == 3) return go(k_backward_std<6, 3>);
+  if (m.nv == 2 && m.nu == 1) return go(k_backward_std<2, 1>);
+  return go(k_backward_std<0, 0>);
 }
 
 // ilqg_selftest_div: the split division (dsmall.h) against nothing but the

@@ -71,6 +71,7 @@ EXPORTS = [
     "ilqg_solver_point_owners",
     "ilqg_model_ctrlrange", "ilqg_solver_set_ctrl_limits", "ilqg_solver_get_ctrl_limits", "ilqg_solver_get_clamped",
     "ilqg_solver_set_cost_schedule", "ilqg_solver_get_cost_schedule", "ilqg_solver_shift_cost_schedule",
+    "ilqg_solver_set_recursion", "ilqg_solver_get_expected",
 ]
 KERNELS = ("rollout", "select", "fd_centre", "fd_cols", "backward", "fd_backward")
 
@@ -622,6 +623,26 @@ class ILQR:
         g, c = ctypes.c_int(0), ctypes.c_int(0)
         _check(lib().ilqg_solver_get_groups(self._h, ctypes.byref(g), ctypes.byref(c)), "get_groups")
         return c.value
+
+    def set_recursion(self, mode: str):
+        """'reference' (default: the backward step of inc/ilqr.h:157-174 as
+        written) or 'standard' (the textbook iLQR step that replaces it: exact
+        diagonal cost Hessians, mu in Quu / Qux only, no c term; meant for
+        set_layout('corrected')): ilqg_solver_set_recursion.  With 'standard'
+        iterate() runs unfused; 'reference' restores the solver as created."""
+        _check(lib().ilqg_solver_set_recursion(self._h, {"reference": 0, "standard": 1}[mode]), "set_recursion")
+
+    def expected(self):
+        """(dV, first_bad) of the last backward pass (ilqg_solver_get_expected):
+        dV (S, 2) = the expected cost change's linear and quadratic terms, so a
+        step of scale alpha is expected to change the cost by
+        alpha dV[:, 0] + alpha^2 dV[:, 1]; first_bad (S,) = the first step that
+        took the indefinite-step fallback, or -1.  Zeros / -1 after a
+        'reference' pass (inc/ilqr.h:157-174 reports neither)."""
+        dV = np.zeros((self.S, 2))
+        bad = np.zeros(self.S, dtype=np.int32)
+        _check(lib().ilqg_solver_get_expected(self._h, _ptr(dV), bad.ctypes.data_as(_c_int_p)), "get_expected")
+        return dV, bad
 
     def set_riccati(self, mode: str):
         """'exact' (bit-identical to the oracle, default) or 'mfma' (matrix-core

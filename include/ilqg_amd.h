@@ -287,6 +287,55 @@ int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled);
    advancing clock by itself.  ILQG_ERR_ARG while the schedule is off, for
    n < 1 or n > N+1, and for new_rows NULL or non-finite.  Synchronises. */
 int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows);
+/* Recursion mode.  REFERENCE (default): the backward step of inc/ilqr.h:157-174
+   as the reference wrote it (outer products of the FD cost gradients for
+   Hessians, mu added to V and kept, factors of 2: SURVEY.md Appendix A Q13,
+   Q15, Q16).  STANDARD replaces inc/ilqr.h:157-174 by the textbook iLQR step
+   in deviation coordinates about the nominal trajectory (no c term); the
+   reference has no counterpart.  For step n = 1..N, with A, B assembled from
+   record n as today (either layout), q = dgdx, r = dgdu of record n,
+   lxx = 2 diag(wq, wv) and luu = 2 diag(wu) the exact Hessians of ilqg_cost
+   (row n of the cost schedule when one is on, else the creation cost; with
+   set_deriv still the solver's cost) and mu from opts.mu / set_mu:
+     Qx = q + A'v   Qu = r + B'v   Qxx = lxx + A'VA   Qux = B'VA   Quu = luu + B'VB
+     Quu_r = luu + B'(V + mu I)B   Qux_r = B'(V + mu I)A   (Tassa, Erez & Todorov 2012, eq. 10)
+     k = -Quu_r^-1 Qu   K = -Quu_r^-1 Qux_r   dV1 += k'Qu   dV2 += 1/2 k'Quu k
+     v <- Qx + K'Quu k + K'Qu + Qux'k
+     V <- Qxx + K'Quu K + K'Qux + Qux'K ;  V <- (V + V')/2
+   (evaluated in the algebraically equal closed-loop form V = lxx + K'luu K +
+   (A+BK)'V(A+BK)); the regulariser does not enter the value update.  The
+   recursion starts from v = dgdx of record 0 and V = lxx of row 0, or from
+   ilqg_solver_set_value's arrays for one pass.  K, k keep their layouts: the
+   rollout's law u = K(x - x*) + alpha k + u* is the one this step assumes.
+   Indefinite step: Quu_r is factored by the pivoted LDLT; a pivot <= 0 or NaN
+   (or a non-finite gain) makes the step take K = 0, k = 0 and add nothing to
+   dV -- V, v go on as for an uncontrolled step -- and flags it.
+   Meant for ILQG_LAYOUT_CORRECTED: in the reference layout with nu > 1 the
+   step reads permuted Jacobians and the cost rises (not enforced).
+   Synchronises like ilqg_solver_set_mu and applies to every backward pass
+   enqueued after it; any other mode is ILQG_ERR_ARG.  With STANDARD on,
+   ilqg_iterate runs rollout, selection, sweep, ilqg_backward unfused (as with
+   control limits); REFERENCE restores the solver exactly as created, the
+   fused sweep included.  Composes with both layouts, set_mu, set_value,
+   set_deriv, fp32 FD, the cost schedule, select_mode 0 and 1, and
+   ilqg_forward_sharded.  Not built here -- ILQG_ERR_UNSUPPORTED, from whichever
+   call comes second: a model with nq != nv (the humanoid: the tangent-space
+   Hessian of a quaternion term is not diagonal), the MFMA engine, control
+   limits, seed groups > 1.  Also not built: a fused/streamed or register
+   formulation, the semi-implicit top block of A (Q10), a mu schedule on the
+   device (the host has first_bad, dV and set_mu to build one). */
+#define ILQG_RECURSION_REFERENCE 0
+#define ILQG_RECURSION_STANDARD 1
+int ilqg_solver_set_recursion(ilqg_solver* s, int mode);
+/* the last backward pass's expected change of the trajectory cost, per seed:
+   dV[nseed][2] = dV1 (linear term, sum of k'Qu) and dV2 (quadratic term, sum of
+   1/2 k'Quu k), so a step of feed-forward scale alpha is expected to change
+   the cost by alpha dV1 + alpha^2 dV2 (accept test: the actual change over
+   that, both negative); first_bad[nseed] = the smallest step n that took the
+   indefinite-step fallback, or -1.  Either pointer may be NULL.  After a
+   REFERENCE pass dV reads 0 and first_bad -1: inc/ilqr.h:157-174, which the
+   STANDARD step replaces, reports neither (no counterpart).  Synchronises. */
+int ilqg_solver_get_expected(ilqg_solver* s, double* dV, int* first_bad);
 /* Riccati recursion (inc/ilqr.h:133-176) engine.  EXACT (default): the
    oracle's loops, bit-identical K, k, V, v (streamed behind the FD sweep on
    cooperative models).  MFMA: every matrix product (B'V, Quu = -2B'VB - 2R,
