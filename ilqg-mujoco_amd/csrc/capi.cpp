@@ -843,10 +843,15 @@ int ilqg_solver_init(ilqg_solver* s, const double* time, const double* qpos, con
   const HostModel& h = m->host;
   int rc = upload_state(s, s->dinit, s->S, time, qpos, qvel, warm, ctrl);
   if (rc) return rc;
+  // NULL means zero, also on a solver initialised with forces before
   if (qfrc_applied)
     HIPCHK(hipMemcpy(s->qfrc_applied.p, qfrc_applied, (size_t)s->S * h.nv * 8, hipMemcpyHostToDevice));
+  else
+    HIPCHK(hipMemset(s->qfrc_applied.p, 0, (size_t)s->S * h.nv * 8));
   if (xfrc_applied)
     HIPCHK(hipMemcpy(s->xfrc_applied.p, xfrc_applied, (size_t)s->S * 6 * h.nbody * 8, hipMemcpyHostToDevice));
+  else
+    HIPCHK(hipMemset(s->xfrc_applied.p, 0, (size_t)s->S * 6 * h.nbody * 8));
   // ILQR ctor: passive rollout with constant ctrl into dArray[N..0]
   TrajDev nom = s->tview(s->traj), di = s->tview(s->dinit);
   HIPCHK(launch_rollout_coop(m->dm, m->Lc, m->C, m->X,

@@ -118,7 +118,8 @@ int ilqg_solver_create(const ilqg_model* m, const ilqg_solver_opts* opts, const 
 void ilqg_solver_free(ilqg_solver* s);
 /* ILQR ctor (inc/ilqr.h:69-97): per seed, d = dmain; initial passive rollout
    with constant ctrl fills the trajectory; then setDInit(dmain).  dmain
-   arrays are nseed x {1, nq, nv, nv, nu}; applied forces may be NULL (zero). */
+   arrays are nseed x {1, nq, nv, nv, nu}; applied forces may be NULL (zero,
+   also when an earlier call on the same solver passed forces). */
 int ilqg_solver_init(ilqg_solver* s, const double* time, const double* qpos, const double* qvel,
                      const double* warm, const double* ctrl, const double* qfrc_applied,
                      const double* xfrc_applied);
