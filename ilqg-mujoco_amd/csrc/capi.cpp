@@ -329,6 +329,24 @@ struct ilqg_solver {
   int recursion = ILQG_RECURSION_REFERENCE;
   bool ex_valid = false;
   DevBuf ex_dV, ex_bad;
+  // regularisation mode (ilqg_solver_set_regularization; device/kernels.h RegDev):
+  // the per-seed schedule state and the trace ring [reg.trace_len][S][8];
+  // reg_iter counts the acceptances enqueued since the mode was switched on
+  // (iteration i writes slot i % trace_len).  With one candidate the rollout
+  // writes cand too (allocated on first use), never the nominal in place.
+  bool reg_on = false;
+  ilqg_reg_opts reg{};
+  DevBuf reg_mu, reg_dmu, reg_cost, reg_valid, reg_status, reg_retries, reg_trace;
+  long reg_iter = 0;
+  // the state as a launch takes it; slot: the trace iteration it writes, < 0 = none
+  RegDev rview(long slot) const {
+    RegDev r{reg_mu.as<double>(), reg_dmu.as<double>(), reg_cost.as<double>(), reg_valid.as<int>(),
+             reg_status.as<int>(), reg_retries.as<int>(), nullptr, reg.factor, reg.mu_min, reg.mu_max, reg.zmin,
+             reg.tol_cost, reg.max_retry};
+    if (slot >= 0 && reg.trace_len > 0)
+      r.trace = reg_trace.as<double>() + (size_t)(slot % reg.trace_len) * S * REG_TRACE;
+    return r;
+  }
   // cost schedule (ilqg_solver_set_cost_schedule): one packed cost row per
   // trajectory point, [P][csz], shared by every seed; sched[sched_cur] is the
   // table in force and the other buffer the target of the next shift (a shift
@@ -430,6 +448,27 @@ struct ilqg_solver {
 static bool fused_ok(const ilqg_model* m);
 void ilqg_solver::choose_fused() {
   fused = !limits && recursion == ILQG_RECURSION_REFERENCE && riccati == ILQG_RICCATI_EXACT && fdprec == ILQG_FD_F64 && fused_ok(model) && sync.p;
+}
+
+// regularisation mode: the nominal trajectory, its start, the gains or the cost
+// were replaced from outside, so cost_nom no longer is the nominal's cost under
+// the next rollout's terms -- the next step is taken unconditionally.  The
+// caller has waited for the solver's launches.
+static int reg_invalidate(ilqg_solver* s) {
+  if (!s->reg_on) return ILQG_OK;
+  HIPCHK(hipMemsetAsync(s->reg_valid.p, 0, s->reg_valid.n, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return ILQG_OK;
+}
+// every seed's mu (per seed, or one value), dmu = 1, status = 0
+static int reg_upload_mu(ilqg_solver* s, const double* mu, double all) {
+  std::vector<double> m(s->S, all), one(s->S, 1.0);
+  if (mu) m.assign(mu, mu + s->S);
+  HIPCHK(hipMemcpyAsync(s->reg_mu.p, m.data(), m.size() * 8, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipMemcpyAsync(s->reg_dmu.p, one.data(), one.size() * 8, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipMemsetAsync(s->reg_status.p, 0, s->reg_status.n, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return ILQG_OK;
 }
 
 static std::vector<double> pack_cost(const HostModel& m, const ilqg_cost* c) {
@@ -861,20 +900,23 @@ int ilqg_solver_init(ilqg_solver* s, const double* time, const double* qpos, con
   HIPCHK(s->sync_all());
   // setDInit(dmain) as the MPC driver does before iterating (src/inverted_pendulum/inverted_pendulum.cpp:21)
   s->initialized = true;
-  return upload_state(s, s->dinit, s->S, time, qpos, qvel, warm, ctrl);
+  rc = upload_state(s, s->dinit, s->S, time, qpos, qvel, warm, ctrl);
+  return rc ? rc : reg_invalidate(s);
 }
 
 int ilqg_solver_set_dinit(ilqg_solver* s, const double* time, const double* qpos, const double* qvel,
                           const double* warm, const double* ctrl) {
   if (!s) return fail(ILQG_ERR_ARG, "null solver");
-  return upload_state(s, s->dinit, s->S, time, qpos, qvel, warm, ctrl);
+  const int rc = upload_state(s, s->dinit, s->S, time, qpos, qvel, warm, ctrl);
+  return rc ? rc : reg_invalidate(s);
 }
 
 int ilqg_solver_set_traj(ilqg_solver* s, const double* time, const double* qpos, const double* qvel,
                          const double* warm, const double* ctrl) {
   if (!s) return fail(ILQG_ERR_ARG, "null solver");
   s->initialized = true;
-  return upload_state(s, s->traj, (size_t)s->S * s->P, time, qpos, qvel, warm, ctrl);
+  const int rc = upload_state(s, s->traj, (size_t)s->S * s->P, time, qpos, qvel, warm, ctrl);
+  return rc ? rc : reg_invalidate(s);
 }
 
 int ilqg_solver_get_traj(ilqg_solver* s, double* time, double* qpos, double* qvel, double* warm, double* ctrl) {
@@ -893,7 +935,7 @@ int ilqg_solver_set_gains(ilqg_solver* s, const double* K, const double* k) {
   HIPCHK(s->sync_all());
   if (K) HIPCHK(hipMemcpy(s->K.p, K, s->K.n, hipMemcpyHostToDevice));
   if (k) HIPCHK(hipMemcpy(s->k.p, k, s->k.n, hipMemcpyHostToDevice));
-  return ILQG_OK;
+  return reg_invalidate(s);
 }
 
 int ilqg_solver_get_gains(ilqg_solver* s, double* K, double* k) {
@@ -975,7 +1017,7 @@ static RollArgs roll_args(ilqg_solver* s, const SeedRange& r, RollChunk ch) {
   const HostModel& h = s->model->host;
   const size_t s0 = r.s0, P = s->P, A = s->A, nx = s->nx;
   const TrajDev nom = toff(s->tview(s->traj), s0 * P, h);
-  const bool multi = s->A > 1;
+  const bool multi = s->A > 1 || s->reg_on;  // (the acceptance needs the candidate beside the nominal)
   if (ch.n_hi >= 0) ch.carry = toff(s->tview(s->carry), s0 * A, h);
   if (s->limits) ch.ulim = s->ulim.as<double>();
   return RollArgs{r.ns, s->A, s->P, nom, multi ? toff(s->tview(s->cand), s0 * A * P, h) : nom, multi ? 1 : 0,
@@ -993,6 +1035,15 @@ static hipError_t forward_range(ilqg_solver* s, const SeedRange& r, hipEvent_t b
     if (e != hipSuccess) return e;
   }
   const RollArgs a = roll_args(s, r, RollChunk{});  // (the selection reads the same views)
+  if (s->reg_on) {
+    // regularisation mode (never with seed groups: r is the whole solver)
+    const RegDev rg = s->rview(s->reg_iter++);
+    return s->timed(1, [&] {
+      return launch_accept(m->dm, r.ns, s->A, s->P, s->opts.select_mode, a.cost_cand, s->alphas.as<double>(),
+                           s->ex_dV.as<double>(), s->sel.as<int>(), s->cost_sel.as<double>(), a.out, a.nominal,
+                           a.dinit, rg, r.st);
+    }, r.st);
+  }
   return s->timed(1, [&] {
     return launch_select(m->dm, r.ns, s->A, s->P, s->opts.select_mode, a.out_is_cand, a.cost_cand,
                          s->sel.as<int>() + r.s0, s->cost_sel.as<double>() + r.s0, a.out, a.nominal, a.dinit, r.st);
@@ -1160,6 +1211,9 @@ int ilqg_forward_sharded(ilqg_solver* s, int rank, int world) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
   if (world < 1 || rank < 0 || rank >= world) return fail(ILQG_ERR_ARG, "rank outside [0, world)");
   if (int rc = limits_rollout_check(s)) return rc;
+  if (s->reg_on)
+    return fail(ILQG_ERR_UNSUPPORTED, "point sharding: the pipelined rollout writes the nominal trajectory in place, "
+                                      "which a rejected step must keep (ilqg_solver_set_regularization(s, NULL) first)");
   if (s->pipe_chunk <= 0 || !s->pipe_flat || s->fused)
     return fail(ILQG_ERR_UNSUPPORTED, "point sharding rides the pipelined iterate (one candidate per seed, the "
                                       "unfused sweep: fp32 FD or the MFMA recursion, flat chunks)");
@@ -1359,6 +1413,11 @@ int ilqg_backward(ilqg_solver* s) {
   s->ex_valid = s->recursion == ILQG_RECURSION_STANDARD;
   HIPCHK(s->timed(4, [&] {
     // the standard recursion (set_recursion keeps limits and the MFMA engine out)
+    if (s->reg_on)
+      return launch_backward_std_reg(m->dm, s->S, s->P, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
+                                     s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
+                                     s->flags(), StdDev{s->cview(), s->cstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
+                                     s->rview(s->reg_iter - 1), s->stream);
     if (s->recursion == ILQG_RECURSION_STANDARD)
       return launch_backward_std(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
                                  s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
@@ -1430,7 +1489,8 @@ int ilqg_iterate(ilqg_solver* s) {
   if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
   if (int rc = limits_rollout_check(s)) return rc;
   if (s->ngroups > 1 && s->fused) return iterate_groups(s);
-  if (!s->fused && s->pipe_chunk > 0) return iterate_pipelined(s);
+  // (the pipelined rollout writes the nominal in place: not in the regularisation mode)
+  if (!s->fused && s->pipe_chunk > 0 && !s->reg_on) return iterate_pipelined(s);
   int rc = ilqg_forward(s);
   if (rc) return rc;
   if (s->fused) {
@@ -1525,6 +1585,7 @@ int ilqg_solver_set_mu(ilqg_solver* s, double mu) {
   if (!s || !(mu == mu)) return fail(ILQG_ERR_ARG, "bad argument");
   HIPCHK(s->sync_all());  // launches already enqueued keep the value they were given
   s->opts.mu = mu;
+  if (s->reg_on) return reg_upload_mu(s, nullptr, mu);
   return ILQG_OK;
 }
 
@@ -1573,6 +1634,9 @@ int ilqg_solver_set_recursion(ilqg_solver* s, int mode) {
   if (!s || (mode != ILQG_RECURSION_REFERENCE && mode != ILQG_RECURSION_STANDARD))
     return fail(ILQG_ERR_ARG, "bad argument");
   const HostModel& h = s->model->host;
+  if (mode == ILQG_RECURSION_REFERENCE && s->reg_on)
+    return fail(ILQG_ERR_UNSUPPORTED, "reference recursion: the regularisation mode runs on the standard one "
+                                      "(ilqg_solver_set_regularization(s, NULL) first)");
   if (mode == ILQG_RECURSION_STANDARD) {
     if (h.nq != h.nv)
       return fail(ILQG_ERR_UNSUPPORTED, "standard recursion: nq != nv (the tangent-space Hessian of a quaternion "
@@ -1616,6 +1680,96 @@ int ilqg_solver_get_expected(ilqg_solver* s, double* dV, int* first_bad) {
   return ILQG_OK;
 }
 
+int ilqg_solver_set_regularization(ilqg_solver* s, const ilqg_reg_opts* o) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (!o) {  // off: the solver as it was (the candidate buffer of a one-candidate solver stays allocated, unused)
+    HIPCHK(s->sync_all());
+    s->reg_on = false;
+    s->reg = ilqg_reg_opts{};
+    return ILQG_OK;
+  }
+  // (written so that a NaN fails)
+  if (!(o->factor > 1) || !std::isfinite(o->factor) || !(o->mu_min >= 0) || !(o->mu_max > o->mu_min) ||
+      !(o->zmin >= 0) || !(o->tol_cost >= 0) || std::isinf(o->mu_min) || std::isinf(o->zmin) ||
+      std::isinf(o->tol_cost))
+    return fail(ILQG_ERR_ARG, "regularization: factor > 1, mu_min >= 0, mu_max > mu_min, zmin >= 0, tol_cost >= 0");
+  if (o->max_retry < 0 || o->max_retry > ILQG_REG_MAXRETRY || o->trace_len < 0 || o->trace_len > ILQG_REG_MAXTRACE)
+    return fail(ILQG_ERR_ARG, "regularization: max_retry in 0 .. 16, trace_len in 0 .. 1024");
+  static_assert(ILQG_REG_MAXRETRY == REG_MAXRETRY && ILQG_REG_TRACE == REG_TRACE, "header and device constants");
+  if (s->recursion != ILQG_RECURSION_STANDARD)
+    return fail(ILQG_ERR_UNSUPPORTED, "regularization: the acceptance test and the restart belong to the standard "
+                                      "recursion (ilqg_solver_set_recursion(s, ILQG_RECURSION_STANDARD) first)");
+  HIPCHK(s->sync_all());  // launches already enqueued keep the mode they were given
+  const size_t S = s->S;
+  if (!s->reg_mu.p) {
+    HIPCHK(s->reg_mu.alloc(S * 8));
+    HIPCHK(s->reg_dmu.alloc(S * 8));
+    HIPCHK(s->reg_cost.alloc(S * 8));
+    HIPCHK(s->reg_valid.alloc(S * 4));
+    HIPCHK(s->reg_status.alloc(S * 4));
+    HIPCHK(s->reg_retries.alloc(S * 4));
+  }
+  if (!s->cand[0].p) {  // one candidate: the rollout's output beside the nominal
+    const HostModel& h = s->model->host;
+    const size_t fld[5] = {1, (size_t)h.nq, (size_t)h.nv, (size_t)h.nv, (size_t)h.nu};
+    for (int f = 0; f < 5; f++) HIPCHK(s->cand[f].alloc(S * s->A * s->P * fld[f] * 8));
+  }
+  HIPCHK(s->reg_trace.alloc((size_t)o->trace_len * S * REG_TRACE * 8));  // (zeroed; empty for trace_len 0)
+  s->reg = *o;
+  s->reg_iter = 0;
+  HIPCHK(hipMemsetAsync(s->reg_valid.p, 0, s->reg_valid.n, s->stream));
+  HIPCHK(hipMemsetAsync(s->reg_retries.p, 0, s->reg_retries.n, s->stream));
+  HIPCHK(hipMemsetAsync(s->reg_cost.p, 0, s->reg_cost.n, s->stream));
+  if (int rc = reg_upload_mu(s, nullptr, s->opts.mu)) return rc;
+  s->reg_on = true;
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_regularization(ilqg_solver* s, ilqg_reg_opts* opts, int* enabled) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (opts) *opts = s->reg;
+  if (enabled) *enabled = s->reg_on ? 1 : 0;
+  return ILQG_OK;
+}
+
+int ilqg_solver_get_reg_state(ilqg_solver* s, double* mu, double* dmu, double* cost_nom, int* valid, int* status,
+                              int* retries) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (!s->reg_on) return fail(ILQG_ERR_ARG, "regularization is off");
+  HIPCHK(s->sync_all());
+  const std::pair<void*, const DevBuf*> out[6] = {{mu, &s->reg_mu},       {dmu, &s->reg_dmu},
+                                                  {cost_nom, &s->reg_cost}, {valid, &s->reg_valid},
+                                                  {status, &s->reg_status}, {retries, &s->reg_retries}};
+  for (const auto& o : out)
+    if (o.first) HIPCHK(hipMemcpy(o.first, o.second->p, o.second->n, hipMemcpyDeviceToHost));
+  return ILQG_OK;
+}
+
+int ilqg_solver_set_reg_mu(ilqg_solver* s, const double* mu) {
+  if (!s || !mu) return fail(ILQG_ERR_ARG, "bad argument");
+  if (!s->reg_on) return fail(ILQG_ERR_ARG, "regularization is off");
+  for (int i = 0; i < s->S; i++)
+    if (!std::isfinite(mu[i]) || mu[i] < 0) return fail(ILQG_ERR_ARG, "regularization: mu must be finite and >= 0");
+  HIPCHK(s->sync_all());
+  return reg_upload_mu(s, mu, 0.0);
+}
+
+int ilqg_solver_get_reg_trace(ilqg_solver* s, double* trace, int* len) {
+  if (!s || !len) return fail(ILQG_ERR_ARG, "bad argument");
+  if (!s->reg_on) return fail(ILQG_ERR_ARG, "regularization is off");
+  const long T = s->reg.trace_len, n = std::min(s->reg_iter, T);
+  *len = (int)n;
+  if (!trace || !n) return ILQG_OK;
+  HIPCHK(s->sync_all());
+  // the ring's oldest slot first
+  const size_t row = (size_t)s->S * REG_TRACE;
+  const long first = s->reg_iter - n;
+  for (long i = 0; i < n; i++)
+    HIPCHK(hipMemcpy(trace + (size_t)i * row, s->reg_trace.as<double>() + (size_t)((first + i) % T) * row, row * 8,
+                     hipMemcpyDeviceToHost));
+  return ILQG_OK;
+}
+
 static bool all_finite(const double* a, size_t n) {
   for (size_t i = 0; i < n; i++)
     if (!std::isfinite(a[i])) return false;
@@ -1628,7 +1782,7 @@ int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows) {
   if (!rows) {  // off: the solver as it was created
     HIPCHK(s->sync_all());
     s->sched_on = false;
-    return ILQG_OK;
+    return reg_invalidate(s);
   }
   if (!all_finite(rows, n)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
   HIPCHK(s->sync_all());  // launches already enqueued keep the rows they were given
@@ -1636,7 +1790,7 @@ int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows) {
     if (!b.p) HIPCHK(b.alloc(n * 8));
   HIPCHK(hipMemcpy(s->sched[s->sched_cur].p, rows, n * 8, hipMemcpyHostToDevice));
   s->sched_on = true;
-  return ILQG_OK;
+  return reg_invalidate(s);
 }
 
 int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled) {
@@ -1669,7 +1823,7 @@ int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_row
   HIPCHK(hipMemcpyAsync(dst, new_rows, (size_t)n * C * 8, hipMemcpyHostToDevice, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   s->sched_cur = 1 - s->sched_cur;
-  return ILQG_OK;
+  return reg_invalidate(s);
 }
 
 int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* enabled) {

@@ -114,6 +114,53 @@ struct StdDev {
 hipError_t launch_backward_std(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr,
                                double* K, double* k, double* V, double* v, RicFlags fl, StdDev sd, hipStream_t st);
 size_t backward_std_lds_bytes(int nv, int nu);
+// the regularisation mode (ilqg_solver_set_regularization; "Reg" here is the
+// Levenberg-Marquardt schedule, not riccati_reg.h's register formulation):
+// per-seed state resident on the device, [S] each.  k_accept (kernels_rollout.hip)
+// decides a step from cost_nom and the last pass's dV and moves mu; the STD
+// recursion's restarting instances (k_backward_std_reg) read mu[s] and raise it
+// when a step is indefinite.  Every expression of the schedule is fp64 in the
+// order written in reg_increase / reg_decrease: the host reference evaluates
+// the same expressions and the decisions agree bit for bit.
+constexpr int REG_MAXRETRY = 16;  // ILQG_REG_MAXRETRY: restarts of one backward pass, at most
+constexpr int REG_TRACE = 8;      // doubles per (iteration, seed) of the trace
+struct RegDev {
+  double* mu = nullptr;
+  double* dmu = nullptr;
+  double* cost_nom = nullptr;  // the nominal trajectory's cost, meaningful while valid[s]
+  int* valid = nullptr;
+  int* status = nullptr;       // 0 running, 1 converged, 2 mu reached mu_max
+  int* retries = nullptr;      // restarts of the last backward pass
+  double* trace = nullptr;     // this iteration's [S][REG_TRACE] slot of the ring, or null
+  double factor = 0, mu_min = 0, mu_max = 0, zmin = 0, tol_cost = 0;
+  int max_retry = 0;
+};
+// dmu = max(dmu f, f); mu = max(mu dmu, mu_min); status 2 once mu >= mu_max
+__host__ __device__ inline void reg_increase(const RegDev& r, double& mu, double& dmu, int& status) {
+  const double d = dmu * r.factor;
+  dmu = d > r.factor ? d : r.factor;
+  const double t = mu * dmu;
+  mu = t > r.mu_min ? t : r.mu_min;
+  if (mu >= r.mu_max) status = 2;
+}
+// dmu = min(dmu / f, 1 / f); mu = mu dmu, or 0 when that is not above mu_min
+__host__ __device__ inline void reg_decrease(const RegDev& r, double& mu, double& dmu) {
+  const double d = dmu / r.factor, i = 1.0 / r.factor;
+  dmu = d < i ? d : i;
+  const double t = mu * dmu;
+  mu = t > r.mu_min ? t : 0.0;
+}
+// launch_backward_std with a restart: mu from rg.mu[s]; an indefinite step
+// raises it and restarts the recursion, at most min(rg.max_retry, REG_MAXRETRY)
+// times per pass and only while rg.status[s] == 0
+hipError_t launch_backward_std_reg(const DevModel& m, int S, int P, const double* deriv, int Ds, TrajDev tr, double* K,
+                                   double* k, double* V, double* v, RicFlags fl, StdDev sd, RegDev rg, hipStream_t st);
+// launch_select's place in the regularisation mode: the step is accepted (the
+// candidate copied to the nominal trajectory and dinit, mu lowered) or rejected
+// (nothing copied, sel = -1, mu raised).  cand is always a buffer of its own.
+hipError_t launch_accept(const DevModel& m, int S, int A, int P, int mode, const double* cost_cand,
+                         const double* alphas, const double* dV, int* sel, double* cost_sel, TrajDev cand,
+                         TrajDev nominal, TrajDev dinit, RegDev rg, hipStream_t st);
 // the reference recursion with the matrix products on the fp64 matrix cores
 // (riccati_mfma.h): one 8-wave workgroup per seed; agrees with the oracle to
 // rounding (the product sums run in the matrix core's order)

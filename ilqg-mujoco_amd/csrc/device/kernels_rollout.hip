@@ -141,6 +141,108 @@ __global__ void k_select(int nq, int nv, int nu, int S, int A, int P, int mode, 
   }
 }
 
+// k_select's place in the regularisation mode (RegDev, kernels.h), one block
+// per seed.  With a valid nominal cost, candidate a is acceptable when
+//   actual = cost_nom - cost[a] > 0  and  actual >= zmin * expected,
+//   expected = -(alpha_a dV1 + alpha_a alpha_a dV2)
+// (a NaN fails both): mode 1 takes the acceptable candidate of lowest cost (a
+// tie: the lower index), mode 0 tests candidate 0 alone.  Accepted: the
+// candidate becomes the nominal trajectory and dinit, cost_nom and cost_sel
+// its cost, mu is lowered, status 1 once actual < tol_cost.  Rejected: nothing
+// is copied, cost_sel keeps the nominal's cost, sel = -1, mu is raised.  A seed
+// whose status is not 0 rejects everything and keeps its mu.  Without a valid
+// nominal cost the choice is k_select's, unconditionally, and mu stays.
+__global__ void k_accept(int nq, int nv, int nu, int S, int A, int P, int mode, const double* cost_cand,
+                         const double* alphas, const double* dV, int* sel, double* cost_sel, TrajDev cand,
+                         TrajDev nom, TrajDev dinit, RegDev rg) {
+  const int s = blockIdx.x;
+  __shared__ int pick_sh;
+  if (threadIdx.x == 0) {
+    const double* cc = cost_cand + (size_t)s * A;
+    // k_select's choice
+    int best = 0;
+    if (mode == 1) {
+      double bc = cc[0];
+      for (int a = 1; a < A; a++) {
+        const double c = cc[a];
+        if (c < bc || (bc != bc && c == c)) { bc = c; best = a; }
+      }
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double mu = rg.mu[s], dmu = rg.dmu[s];
+    int status = rg.status[s];
+    const double mu_before = mu, cn = rg.cost_nom[s], dV1 = dV[2 * (size_t)s], dV2 = dV[2 * (size_t)s + 1];
+    auto expected = [&](int a) { return -(alphas[a] * dV1 + alphas[a] * alphas[a] * dV2); };
+    int pick = -1;
+    double t0 = nan, t3 = nan;
+    if (!rg.valid[s]) {
+      pick = best;
+      rg.valid[s] = 1;
+    } else {
+      t0 = cn;
+      t3 = expected(best);
+      if (status == 0) {
+        double pc = 0;
+        for (int a = 0; a < (mode == 1 ? A : 1); a++) {
+          const double actual = cn - cc[a];
+          if (actual > 0 && actual >= rg.zmin * expected(a) && (pick < 0 || cc[a] < pc)) {
+            pick = a;
+            pc = cc[a];
+          }
+        }
+        if (pick >= 0) {
+          t3 = expected(pick);
+          reg_decrease(rg, mu, dmu);
+          if (cn - cc[pick] < rg.tol_cost) status = 1;
+        } else {
+          reg_increase(rg, mu, dmu, status);
+        }
+      }
+    }
+    if (pick >= 0) {
+      rg.cost_nom[s] = cc[pick];
+      cost_sel[s] = cc[pick];
+    }
+    sel[s] = pick;
+    rg.mu[s] = mu;
+    rg.dmu[s] = dmu;
+    rg.status[s] = status;
+    if (rg.trace) {
+      double* t = rg.trace + (size_t)s * REG_TRACE;
+      t[0] = t0;
+      t[1] = cc[best];
+      t[2] = (double)pick;
+      t[3] = t3;
+      t[4] = mu_before;
+      t[5] = mu;
+      // (6, 7: the backward pass that follows)
+      t[6] = nan;
+      t[7] = nan;
+    }
+    pick_sh = pick;
+  }
+  __syncthreads();
+  const int pick = pick_sh;
+  if (pick < 0) return;
+  const size_t src0 = ((size_t)s * A + pick) * P, dst0 = (size_t)s * P;
+  for (int p = threadIdx.x; p < P; p += blockDim.x) {
+    nom.time[dst0 + p] = cand.time[src0 + p];
+    for (int i = 0; i < nq; i++) nom.qpos[(dst0 + p) * nq + i] = cand.qpos[(src0 + p) * nq + i];
+    for (int i = 0; i < nv; i++) nom.qvel[(dst0 + p) * nv + i] = cand.qvel[(src0 + p) * nv + i];
+    for (int i = 0; i < nv; i++) nom.warm[(dst0 + p) * nv + i] = cand.warm[(src0 + p) * nv + i];
+    for (int i = 0; i < nu; i++) nom.ctrl[(dst0 + p) * nu + i] = cand.ctrl[(src0 + p) * nu + i];
+  }
+  // setDInit(dArray[N]), inc/ilqr.h:183
+  if (threadIdx.x == 0) {
+    const size_t sp = src0 + (P - 1);
+    dinit.time[s] = cand.time[sp];
+    for (int i = 0; i < nq; i++) dinit.qpos[(size_t)s * nq + i] = cand.qpos[sp * nq + i];
+    for (int i = 0; i < nv; i++) dinit.qvel[(size_t)s * nv + i] = cand.qvel[sp * nv + i];
+    for (int i = 0; i < nv; i++) dinit.warm[(size_t)s * nv + i] = cand.warm[sp * nv + i];
+    for (int i = 0; i < nu; i++) dinit.ctrl[(size_t)s * nu + i] = cand.ctrl[sp * nu + i];
+  }
+}
+
 }  // namespace
 
 static bool use_dual() {
@@ -184,6 +286,16 @@ hipError_t launch_select(const DevModel& m, int S, int A, int P, int mode, int c
   hipLaunchKernelGGL(k_select, dim3(S), dim3(256), 0, st, m.nq, m.nv, m.nu, S, A, P, mode, copy_cand, cost_cand,
                      sel, cost_sel, cand, nominal, dinit);
   return hipGetLastError();
+}
+
+hipError_t launch_accept(const DevModel& m, int S, int A, int P, int mode, const double* cost_cand,
+                         const double* alphas, const double* dV, int* sel, double* cost_sel, TrajDev cand,
+                         TrajDev nominal, TrajDev dinit, RegDev rg, hipStream_t st) {
+  if (!cost_cand || !alphas || !dV || !sel || !cost_sel || !cand.qpos || cand.qpos == nominal.qpos || !rg.mu ||
+      !rg.dmu || !rg.cost_nom || !rg.valid || !rg.status)
+    return hipErrorInvalidValue;
+  return launch(k_accept, (unsigned)S, 256u, 0, st, m.nq, m.nv, m.nu, S, A, P, mode, cost_cand, alphas, dV, sel,
+                cost_sel, cand, nominal, dinit, rg);
 }
 
 hipError_t launch_step_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,

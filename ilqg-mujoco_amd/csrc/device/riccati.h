@@ -705,12 +705,26 @@ __device__ inline int box_solve(int nu, const BoxLds& L, double* Mm, const doubl
 // extra LDS of an STD instance, in doubles: the unregularised Quu, lxx, luu
 __host__ __device__ constexpr size_t std_lds_doubles(size_t nv, size_t nu) { return nu * nu + 2 * nv + nu; }
 
-template <int NV_, int NU_, bool BOX = false, bool STD = false, class MD>
+//
+// REG (with STD; RegDev, kernels.h): mu is the seed's own, rg.mu[s], and an
+// indefinite step raises it (reg_increase) and restarts the recursion from
+// step 1 -- the same V0, v0 (Vg, vg are written only behind the last attempt),
+// the record prefetch primed again -- while fewer than rg.max_retry restarts
+// were used and rg.status[s] is 0; otherwise the step takes the fallback above.
+// The restart is a backward jump taken by the whole wave (box_uni) under a
+// counter bounded by the constant REG_MAXRETRY: a pass costs at most
+// REG_MAXRETRY + 1 plain passes and waits on nothing.  A jump, not a loop
+// around the body, so that the instances without REG compile from the same
+// statements as before.
+
+template <int NV_, int NU_, bool BOX = false, bool STD = false, bool REG = false, class MD>
 __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, int P, double dt, double mu,
                                      const double* deriv, int Ds, TrajDev tr, double* Kg, double* kg, double* Vg,
                                      double* vg, int s, int tid, double* sh, const unsigned* done, unsigned target,
-                                     unsigned* fault, RicFlags fl, BoxDev bx = BoxDev{}, StdDev sd = StdDev{}) {
+                                     unsigned* fault, RicFlags fl, BoxDev bx = BoxDev{}, StdDev sd = StdDev{},
+                                     RegDev rg = RegDev{}) {
   static_assert(!(BOX && STD), "the boxed step is the reference recursion's");
+  static_assert(!REG || STD, "the restart belongs to the standard step");
 #ifndef ILQG_RIC_LDS
   // bundled small models: the register/exchange formulation (riccati_reg.h)
   // (a BOX or STD instance is always the LDS formulation below)
@@ -810,8 +824,17 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
 #ifdef ILQG_STAMPS
   unsigned long long bst_prev = 0;
 #endif
+  // REG: the seed's schedule state (every lane loads the same words)
+  double dmu = 1.0;
+  int rstatus = 0, retries = 0;
+  if constexpr (REG) {
+    mu = rg.mu[s];
+    dmu = rg.dmu[s];
+    rstatus = rg.status[s];
+  }
 
   // initV at the terminal point dArray[0], inc/ilqr.h:100-107
+  [[maybe_unused]] restart:
   {
     ready(0);
     const double* q0 = deriv + ((size_t)s * P + 0) * Ds + 2 * nv * nv + nv * nu;
@@ -1072,6 +1095,19 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       for (int e = tid; e < nu * nx; e += BW_THREADS) fin &= fabs(Kl[e]) <= 1.7976931348623157e308 ? 1 : 0;
       if (tid < nu) fin &= fabs(kl[tid]) <= 1.7976931348623157e308 ? 1 : 0;
       ok &= __ballot(!fin) == 0ull ? 1 : 0;
+      if constexpr (REG) {
+        // restart at a larger mu: decided from wave-uniform values, taken by every lane
+        const int cap = rg.max_retry < REG_MAXRETRY ? rg.max_retry : REG_MAXRETRY;
+        if (box_uni(!ok && retries < cap && rstatus == 0)) {
+          reg_increase(rg, mu, dmu, rstatus);
+          retries++;
+          dV1 = 0;
+          dV2 = 0;
+          first_bad = -1;
+          __syncthreads();  // the step's LDS reads are done before initV rewrites V, v, dl
+          goto restart;
+        }
+      }
       if (box_uni(!ok)) {
         if (first_bad < 0) first_bad = n;
         for (int e = tid; e < nu * nx; e += BW_THREADS) Kl[e] = 0.0;
@@ -1229,6 +1265,16 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
       sd.dV[2 * (size_t)s] = dV1;
       sd.dV[2 * (size_t)s + 1] = dV2;
       sd.bad[s] = first_bad;
+      if constexpr (REG) {
+        rg.mu[s] = mu;
+        rg.dmu[s] = dmu;
+        rg.status[s] = rstatus;
+        rg.retries[s] = retries;
+        if (rg.trace) {
+          rg.trace[(size_t)s * REG_TRACE + 6] = mu;
+          rg.trace[(size_t)s * REG_TRACE + 7] = (double)(retries + 100 * rstatus);
+        }
+      }
     }
   }
 }

@@ -90,6 +90,19 @@ __global__ __launch_bounds__(BW_THREADS) void k_backward_std(DevModel m, int nq,
                                        threadIdx.x, sh, nullptr, 0u, nullptr, fl, BoxDev{}, sd);
 }
 
+// the standard recursion in the regularisation mode (RegDev, kernels.h): mu per
+// seed from rg.mu, an indefinite step restarts the pass at a larger one; never
+// streamed.  Instances of their own: k_backward_std's keep their code.
+template <int NV_, int NU_>
+__global__ __launch_bounds__(BW_THREADS) void k_backward_std_reg(DevModel m, int nq, int nv_rt, int nu_rt, int P,
+                                                                 double dt, const double* deriv, int Ds, TrajDev tr,
+                                                                 double* Kg, double* kg, double* Vg, double* vg,
+                                                                 RicFlags fl, StdDev sd, RegDev rg) {
+  extern __shared__ double sh[];
+  backward_seed<NV_, NU_, false, true, true>(m, nq, nv_rt, nu_rt, P, dt, 0.0, deriv, Ds, tr, Kg, kg, Vg, vg,
+                                             blockIdx.x, threadIdx.x, sh, nullptr, 0u, nullptr, fl, BoxDev{}, sd, rg);
+}
+
 template <int NV, int NU>
 hipError_t launch_box_t(const DevModel& m, int S, int P, double mu, const double* deriv, int Ds, TrajDev tr, double* K,
                         double* k, double* V, double* v, RicFlags fl, BoxDev bx, size_t lds, hipStream_t st) {
@@ -217,6 +230,24 @@ hipError_t launch_backward_std(const DevModel& m, int S, int P, double mu, const
   if (m.nv == 6 && m.nu == 3) return go(k_backward_std<6, 3>);
   if (m.nv == 2 && m.nu == 1) return go(k_backward_std<2, 1>);
   return go(k_backward_std<0, 0>);
+}
+
+hipError_t launch_backward_std_reg(const DevModel& m, int S, int P, const double* deriv, int Ds, TrajDev tr, double* K,
+                                   double* k, double* V, double* v, RicFlags fl, StdDev sd, RegDev rg,
+                                   hipStream_t st) {
+  if (m.nu > 32 || m.nq != m.nv || !sd.cost.wq || !sd.cost.wv || !sd.cost.wu || !sd.dV || !sd.bad)
+    return hipErrorInvalidValue;
+  if (!rg.mu || !rg.dmu || !rg.status || !rg.retries || rg.max_retry < 0 || rg.max_retry > REG_MAXRETRY)
+    return hipErrorInvalidValue;
+  const size_t lds = backward_std_lds_bytes(m.nv, m.nu);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const auto go = [&](auto kern) {
+    return launch(kern, (unsigned)S, (unsigned)BW_THREADS, lds, st, m, m.nq, m.nv, m.nu, P, m.opt_timestep, deriv, Ds,
+                  tr, K, k, V, v, fl, sd, rg);
+  };
+  if (m.nv == 6 && m.nu == 3) return go(k_backward_std_reg<6, 3>);
+  if (m.nv == 2 && m.nu == 1) return go(k_backward_std_reg<2, 1>);
+  return go(k_backward_std_reg<0, 0>);
 }
 
 // ilqg_selftest_div: the split division (dsmall.h) against nothing but the

@@ -72,7 +72,17 @@ EXPORTS = [
     "ilqg_model_ctrlrange", "ilqg_solver_set_ctrl_limits", "ilqg_solver_get_ctrl_limits", "ilqg_solver_get_clamped",
     "ilqg_solver_set_cost_schedule", "ilqg_solver_get_cost_schedule", "ilqg_solver_shift_cost_schedule",
     "ilqg_solver_set_recursion", "ilqg_solver_get_expected",
+    "ilqg_solver_set_regularization", "ilqg_solver_get_regularization", "ilqg_solver_get_reg_state",
+    "ilqg_solver_set_reg_mu", "ilqg_solver_get_reg_trace",
 ]
+REG_MAXRETRY, REG_MAXTRACE, REG_TRACE = 16, 1024, 8
+REG_TRACE_FIELDS = ("cost_nom", "cost_best", "chosen", "expected", "mu_before", "mu_accept", "mu_backward", "code")
+
+
+class _RegOpts(ctypes.Structure):
+    _fields_ = [("factor", ctypes.c_double), ("mu_min", ctypes.c_double), ("mu_max", ctypes.c_double),
+                ("zmin", ctypes.c_double), ("tol_cost", ctypes.c_double), ("max_retry", ctypes.c_int),
+                ("trace_len", ctypes.c_int)]
 KERNELS = ("rollout", "select", "fd_centre", "fd_cols", "backward", "fd_backward")
 
 _lib = None
@@ -643,6 +653,61 @@ class ILQR:
         bad = np.zeros(self.S, dtype=np.int32)
         _check(lib().ilqg_solver_get_expected(self._h, _ptr(dV), bad.ctypes.data_as(_c_int_p)), "get_expected")
         return dV, bad
+
+    def set_regularization(self, opts=None, *, factor=1.6, mu_min=1e-6, mu_max=1e10, zmin=0.0, tol_cost=0.0,
+                           max_retry=REG_MAXRETRY, trace_len=0):
+        """the iLQR outer loop on the device, per seed (ilqg_solver_set_regularization;
+        needs set_recursion('standard')): forward_pass() accepts a step when
+        actual > 0 and actual >= zmin * expected and lowers mu, or rejects it
+        (nominal trajectory untouched, costs()[1] == -1) and raises mu; the
+        backward pass restarts at a larger mu when a step is indefinite, at
+        most max_retry times; a seed stops once an accepted reduction is below
+        tol_cost.  opts: True / a dict of the keyword options to switch it on,
+        None / False to switch it off."""
+        if opts is None or opts is False:
+            _check(lib().ilqg_solver_set_regularization(self._h, None), "set_regularization")
+            return
+        kw = dict(factor=factor, mu_min=mu_min, mu_max=mu_max, zmin=zmin, tol_cost=tol_cost, max_retry=max_retry,
+                  trace_len=trace_len)
+        if isinstance(opts, dict):
+            kw.update(opts)
+        o = _RegOpts(**kw)
+        _check(lib().ilqg_solver_set_regularization(self._h, ctypes.byref(o)), "set_regularization")
+
+    def regularization(self):
+        """the options in force as a dict, or None while the mode is off"""
+        o, on = _RegOpts(), ctypes.c_int(0)
+        _check(lib().ilqg_solver_get_regularization(self._h, ctypes.byref(o), ctypes.byref(on)), "get_regularization")
+        return {n: getattr(o, n) for n, _ in _RegOpts._fields_} if on.value else None
+
+    def reg_state(self):
+        """per seed: dict of mu, dmu, cost_nom (S,) float64 and valid, status
+        (0 running, 1 converged, 2 mu reached mu_max), retries (S,) int32
+        (ilqg_solver_get_reg_state; synchronises)"""
+        f = {n: np.zeros(self.S) for n in ("mu", "dmu", "cost_nom")}
+        i = {n: np.zeros(self.S, dtype=np.int32) for n in ("valid", "status", "retries")}
+        _check(lib().ilqg_solver_get_reg_state(self._h, *(_ptr(a) for a in f.values()),
+                                               *(a.ctypes.data_as(_c_int_p) for a in i.values())), "get_reg_state")
+        return {**f, **i}
+
+    def set_reg_mu(self, mu):
+        """mu per seed (a scalar is repeated); dmu = 1 and status = 0 again (ilqg_solver_set_reg_mu)"""
+        mu = np.asarray(mu, dtype=np.float64)
+        mu = np.full(self.S, float(mu)) if mu.ndim == 0 else np.ascontiguousarray(mu.ravel())
+        if mu.size != self.S:
+            raise IlqgError(f"set_reg_mu: {self.S} values")
+        _check(lib().ilqg_solver_set_reg_mu(self._h, _ptr(mu)), "set_reg_mu")
+
+    def reg_trace(self) -> np.ndarray:
+        """(iterations, S, 8) float64, oldest first: REG_TRACE_FIELDS per
+        (iteration, seed) (ilqg_solver_get_reg_trace; synchronises once, so
+        iterate() can be enqueued N times and the history read afterwards)"""
+        n = ctypes.c_int(0)
+        _check(lib().ilqg_solver_get_reg_trace(self._h, None, ctypes.byref(n)), "get_reg_trace")
+        T = self.regularization()["trace_len"]
+        buf = np.zeros((max(T, 1), self.S, REG_TRACE))
+        _check(lib().ilqg_solver_get_reg_trace(self._h, _ptr(buf), ctypes.byref(n)), "get_reg_trace")
+        return buf[:n.value].copy()
 
     def set_riccati(self, mode: str):
         """'exact' (bit-identical to the oracle, default) or 'mfma' (matrix-core

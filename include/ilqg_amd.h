@@ -323,8 +323,8 @@ int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_row
    call comes second: a model with nq != nv (the humanoid: the tangent-space
    Hessian of a quaternion term is not diagonal), the MFMA engine, control
    limits, seed groups > 1.  Also not built: a fused/streamed or register
-   formulation, the semi-implicit top block of A (Q10), a mu schedule on the
-   device (the host has first_bad, dV and set_mu to build one). */
+   formulation, the semi-implicit top block of A (Q10).  The mu schedule and
+   the accept test are ilqg_solver_set_regularization below. */
 #define ILQG_RECURSION_REFERENCE 0
 #define ILQG_RECURSION_STANDARD 1
 int ilqg_solver_set_recursion(ilqg_solver* s, int mode);
@@ -337,6 +337,89 @@ int ilqg_solver_set_recursion(ilqg_solver* s, int mode);
    REFERENCE pass dV reads 0 and first_bad -1: inc/ilqr.h:157-174, which the
    STANDARD step replaces, reports neither (no counterpart).  Synchronises. */
 int ilqg_solver_get_expected(ilqg_solver* s, double* dV, int* first_bad);
+/* Regularisation mode: the iLQR outer loop (Tassa, Erez & Todorov 2012, II-F)
+   on the device, per seed and without a host sync -- step acceptance, the
+   mu / dmu schedule, a backward pass that restarts at a larger mu, a stop.
+   Off by default; needs ILQG_RECURSION_STANDARD; the reference has no
+   counterpart.  Per seed the device keeps mu, dmu, the nominal trajectory's
+   cost and whether it is valid, a status (0 running, 1 converged, 2 mu reached
+   mu_max) and the restart count of the last backward pass.  Every expression
+   below is fp64, evaluated in the order written (f = factor):
+     increase:  dmu = max(dmu f, f);  mu = max(mu dmu, mu_min);  mu >= mu_max: status = 2
+     decrease:  dmu = min(dmu / f, 1 / f);  t = mu dmu;  mu = t > mu_min ? t : 0
+   ilqg_solver_set_regularization(s, opts) switches the mode on: mu[s] = the
+   solver's mu (opts.mu at creation or the last ilqg_solver_set_mu), dmu = 1,
+   status 0, the nominal cost invalid, the trace empty.  NULL switches it off:
+   the solver is then exactly as it was before.  ILQG_ERR_ARG unless
+   factor > 1, mu_min >= 0, mu_max > mu_min, zmin >= 0, tol_cost >= 0,
+   0 <= max_retry <= ILQG_REG_MAXRETRY, 0 <= trace_len <= ILQG_REG_MAXTRACE.
+   Synchronises like ilqg_solver_set_mu.  With the mode on:
+   - ilqg_forward (and the one inside ilqg_iterate) decides the step per seed.
+     For candidate a, actual = cost_nom - cost[a] and expected =
+     -(alpha_a dV1 + alpha_a alpha_a dV2) with the last backward pass's dV; a is
+     acceptable when actual > 0 && actual >= zmin expected (a NaN fails both).
+     select_mode 1 takes the acceptable candidate of lowest cost (a tie: the
+     lower index), select_mode 0 tests candidate 0 only.  Accepted: the
+     candidate becomes the nominal trajectory and dinit, cost_nom its cost, the
+     decrease is applied, and status becomes 1 when actual < tol_cost.
+     Rejected: the nominal trajectory, dinit and the selected cost
+     (ilqg_solver_device_costs) are untouched, ilqg_solver_get_costs reports
+     selected = -1 (only in this mode), and the increase is applied.  A seed
+     whose status is not 0 is frozen: every step is rejected and mu stays.
+     While the nominal cost is invalid the choice is the plain selection's,
+     unconditionally, and mu stays; it is invalid after enabling the mode and
+     after ilqg_solver_init, set_traj, set_dinit, set_gains,
+     set_cost_schedule and shift_cost_schedule.
+   - ilqg_backward (and the one inside ilqg_iterate) reads mu[s].  A step that
+     is indefinite by the STANDARD test raises mu (the increase) and restarts
+     the recursion from step 1, from the same V0, v0 (ilqg_solver_set_value's
+     on every attempt of that pass), while fewer than max_retry restarts were
+     used and status is 0; otherwise the pass completes with the STANDARD
+     fallback and first_bad.  dV and first_bad are the last attempt's.  A pass
+     costs at most max_retry + 1 plain ones.
+   - ilqg_iterate runs rollout, acceptance, sweep, ilqg_backward unfused.  The
+     sweep of a rejected seed is not skipped: it reproduces its records.
+   - ilqg_solver_set_mu sets every seed's mu (dmu = 1, status = 0).
+   Composes with both layouts, the cost schedule, fp32 FD, set_value,
+   set_deriv and both select_modes.  ILQG_ERR_UNSUPPORTED, from whichever call
+   comes second: ILQG_RECURSION_REFERENCE (so also everything STANDARD
+   refuses), and ilqg_forward_sharded while the mode is on. */
+#define ILQG_REG_MAXRETRY 16
+#define ILQG_REG_MAXTRACE 1024
+#define ILQG_REG_TRACE 8
+typedef struct ilqg_reg_opts {
+  double factor;   /* f > 1 (Tassa: 1.6) */
+  double mu_min;   /* >= 0 (1e-6) */
+  double mu_max;   /* > mu_min (1e10) */
+  double zmin;     /* >= 0: the least accepted actual / expected */
+  double tol_cost; /* >= 0, absolute: an accepted reduction below it ends the seed (status 1) */
+  int max_retry;   /* restarts of one backward pass, 0 .. ILQG_REG_MAXRETRY */
+  int trace_len;   /* iterations kept in the trace ring, 0 .. ILQG_REG_MAXTRACE */
+} ilqg_reg_opts;
+int ilqg_solver_set_regularization(ilqg_solver* s, const ilqg_reg_opts* opts);
+/* the options in force (zeros while off) and whether the mode is on; either
+   pointer may be NULL */
+int ilqg_solver_get_regularization(ilqg_solver* s, ilqg_reg_opts* opts, int* enabled);
+/* the per-seed state, nseed entries each, any pointer may be NULL; valid:
+   whether cost_nom is the nominal trajectory's cost.  ILQG_ERR_ARG while the
+   mode is off.  Synchronises. */
+int ilqg_solver_get_reg_state(ilqg_solver* s, double* mu, double* dmu, double* cost_nom, int* valid, int* status,
+                              int* retries);
+/* mu per seed (nseed values, finite and >= 0); resets dmu to 1 and status to 0.
+   ILQG_ERR_ARG while the mode is off.  Synchronises. */
+int ilqg_solver_set_reg_mu(ilqg_solver* s, const double* mu);
+/* the trace, oldest iteration first: *len iterations (at most trace_len) of
+   nseed x ILQG_REG_TRACE doubles; trace may be NULL (the length alone) and
+   must hold trace_len iterations otherwise.  One iteration = one ilqg_forward
+   and the ilqg_backward after it.  Per (iteration, seed):
+     0 the nominal cost before (NaN while invalid)   1 the best candidate's cost
+     2 the chosen index, or -1                       3 the expected reduction of the
+     4 mu before the decision                          tested candidate (NaN while invalid)
+     5 mu after it                                   6 mu after the backward pass
+     7 restarts + 100 status after the backward pass (6, 7: NaN until it ran)
+   so N ilqg_iterate calls can be enqueued back to back and the history read
+   once.  ILQG_ERR_ARG while the mode is off.  Synchronises. */
+int ilqg_solver_get_reg_trace(ilqg_solver* s, double* trace, int* len);
 /* Riccati recursion (inc/ilqr.h:133-176) engine.  EXACT (default): the
    oracle's loops, bit-identical K, k, V, v (streamed behind the FD sweep on
    cooperative models).  MFMA: every matrix product (B'V, Quu = -2B'VB - 2R,
