@@ -260,6 +260,9 @@ struct ilqg_solver {
   // schedule knobs, read once at creation (ILQG_FD_SNAP, ILQG_PLAN, ILQG_PLAN_K,
   // ILQG_PLAN_P0): the launch and the debug_plan hook use the same values
   bool snap_on = true, snap_poison = false, plan_on = false;
+  // ILQG_NT_REPLAY, read at creation: the FD teams' Newton loops end once their
+  // state repeats (FdFused.nt_replay / FdArgs.nt_replay); 0 = every iteration runs
+  int nt_replay = 1;
   float plan_k = 3.0f;
   int plan_p0 = 8;
   // debug_plant_schedule: one-shot (slot, item) pairs written into the next
@@ -718,6 +721,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
   CostDev cd{c, c + nq, c + 2 * nq, c + 3 * nq, c + 3 * nq + nv, c + 3 * nq + 2 * nv,
              c + 3 * nq + 3 * nv, c + 3 * nq + 3 * nv + nu, c + 3 * nq + 3 * nv + 2 * nu};
   TrajDev st{s.time.as<double>(), s.qpos.as<double>(), s.qvel.as<double>(), s.warm.as<double>(), s.ctrl.as<double>()};
+  const int nt_replay = getenv_int("ILQG_NT_REPLAY", 1) != 0 ? 1 : 0;  // read per call: no solver here
   if (fused_ok(m)) {
     // n points as n one-point trajectories through the fused sweep (no backward roles)
     const int Dp = round16(D), WCp = round16(h.nv + 1);
@@ -732,6 +736,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     a.tr = st; a.S = n; a.P = 1; a.nB = 0; a.nv = h.nv; a.nut = fd_nut(h);
     a.Dp = Dp; a.WCp = WCp; a.qfrc_applied = s.qa.as<double>(); a.xfrc_applied = s.xf.as<double>(); a.cost = cd;
     a.cw = cw.as<double>(); a.deriv = outp.as<double>(); a.sync = sy.as<unsigned>(); a.fault = fl.as<unsigned>();
+    a.nt_replay = nt_replay;
     HIPCHK(launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, m->stream, 0));
     HIPCHK(hipStreamSynchronize(m->stream));
     unsigned flt = 0;
@@ -741,7 +746,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     return ILQG_OK;
   } else {
     const FdArgs fa{st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd, 0, s.warm_c.as<double>(),
-                    s.cost_c.as<double>(), s.out.as<double>(), D, m->stream};
+                    s.cost_c.as<double>(), s.out.as<double>(), D, m->stream, nt_replay};
     HIPCHK(launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, fa));
     HIPCHK(launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, fa));
   }
@@ -775,6 +780,7 @@ int ilqg_solver_create(const ilqg_model* mc, const ilqg_solver_opts* o, const il
   s->WCp = round16(h.nv + 1);
   s->fused = fused_ok(m);
   s->nut = fd_nut(h);
+  s->nt_replay = getenv_int("ILQG_NT_REPLAY", 1) != 0 ? 1 : 0;
   s->host_alphas.assign(o->nalpha, 1.0);
   if (o->alphas) std::copy(o->alphas, o->alphas + o->nalpha, s->host_alphas.begin());
   s->opts.alphas = nullptr;
@@ -1281,6 +1287,7 @@ static hipError_t fused_launch(ilqg_solver* s, const SeedRange& r, int mode, boo
   a.V = s->V.as<double>() + s0 * nx * nx;
   a.v = s->v.as<double>() + s0 * nx;
   a.fl = s->flags();
+  a.nt_replay = s->nt_replay;
   {
     // FD teams' issue priority by ticket slot (permille of the FD items; 0 = off)
     const unsigned nit = (unsigned)(r.ns * s->P * (1 + (s->halves ? 2 : 1) * (s->nut + 2 * h.nv)));
@@ -1344,7 +1351,7 @@ static FdArgs fd_args(ilqg_solver* s, int sd, int p0, int npts, int P, hipStream
   return FdArgs{toff(s->tview(s->traj), pt0, h), npts, P, s->qfrc_applied.as<double>() + (size_t)sd * h.nv,
                 s->xfrc_applied.as<double>() + (size_t)sd * 6 * h.nbody, s->cview(p0), s->cstride(),
                 s->warm_c.as<double>() + pt0 * h.nv, s->cost_c.as<double>() + pt0,
-                s->deriv.as<double>() + pt0 * s->Dp, s->Dp, st};
+                s->deriv.as<double>() + pt0 * s->Dp, s->Dp, st, s->nt_replay};
 }
 
 int ilqg_fd_sweep(ilqg_solver* s) {

@@ -37,6 +37,7 @@ __device__ inline Team make_team(const auto& L, const auto& C) {
   T.ci = T.iw + L.ni;
   T.tid = threadIdx.x & (TEAM - 1);  // lane within this wave (two-wave teams: one Team per wave)
   T.nt = TEAM;  // every cooperative kernel is launched with one 64-lane wavefront
+  T.replay = 0;  // the FD kernels set it (ILQG_NT_REPLAY)
   return T;
 }
 
@@ -223,8 +224,11 @@ inline int debug_stamps(unsigned long long* acc, unsigned long long* cnt, int re
   (void)hipMemcpyFromSymbol(&nw[1], HIP_SYMBOL(g_newton_calls), 8);
   acc[44] = nw[0];
   acc[45] = nw[1];
+  // the Newton iterations the replay exit skipped (ILQG_NT_REPLAY), past the stamp ids
+  (void)hipMemcpyFromSymbol(&acc[60], HIP_SYMBOL(g_newton_skipped), 8);
   if (reset) {
     unsigned long long z[STAMP_NG] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_newton_skipped), z, 8);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_newton_iters), z, 8);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_newton_calls), z, 8);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_acc), z, sizeof(z));

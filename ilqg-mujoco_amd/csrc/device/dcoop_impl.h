@@ -12,6 +12,7 @@ struct Team {
   real* c;   // CoopLayout doubles
   int* ci;     // CoopLayout ints
   int tid, nt;
+  int replay;  // the Newton loops' replay exit (ILQG_NT_REPLAY, below): set by the FD kernels, else 0
 };
 
 // Team synchronisation: team_sync() (dsmall.h).
@@ -36,8 +37,11 @@ static __device__ unsigned long long g_ls[8];
 // the same counted per workgroup in LDS (lane 0 of wave 0) and added to the
 // globals once when the workgroup ends: per-event global atomics from
 // thousands of teams distorted the timings they measure ([8], [9]: Newton
-// iterations and solver calls)
-__shared__ unsigned long long s_cnt[10];
+// iterations and solver calls; [10]: Newton iterations the replay exit
+// skipped, ILQG_NT_REPLAY)
+static __device__ unsigned long long g_newton_skipped;
+constexpr int CNT_N = 11;
+__shared__ unsigned long long s_cnt[CNT_N];
 __device__ __forceinline__ void cnt_add_g(unsigned long long* g, unsigned long long v) {
   if (v) __hip_atomic_fetch_add(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -47,6 +51,7 @@ __device__ __forceinline__ void cnt_flush() {
   cnt_add_g(g_ls + 0, c0); cnt_add_g(g_ls + 1, c1); cnt_add_g(g_ls + 2, c2); cnt_add_g(g_ls + 3, c3);
   cnt_add_g(g_ls + 4, c4); cnt_add_g(g_ls + 5, c5); cnt_add_g(g_ls + 6, c6); cnt_add_g(g_ls + 7, c7);
   cnt_add_g(&g_newton_iters, c8); cnt_add_g(&g_newton_calls, c9);
+  cnt_add_g(&g_newton_skipped, s_cnt[10]);
 }
 #define CNT_ADD(i, v)                     \
   do {                                    \
@@ -78,7 +83,7 @@ __shared__ unsigned long long s_stamp_acc[STAMP_N], s_stamp_cnt[STAMP_N], s_stam
 #define STAMP_INIT()                                                         \
   do {                                                                       \
     if (threadIdx.x == 0) {                                                  \
-      for (int i_ = 0; i_ < 10; i_++) s_cnt[i_] = 0;                         \
+      for (int i_ = 0; i_ < CNT_N; i_++) s_cnt[i_] = 0;                      \
       if (STAMP_BLOCK()) {                                                   \
         for (int i_ = 0; i_ < STAMP_N; i_++) s_stamp_acc[i_] = s_stamp_cnt[i_] = 0; \
         s_stamp_prev = s_stamp_prevb = s_stamp_prevc = __builtin_amdgcn_s_memtime();         \
@@ -2695,6 +2700,30 @@ __device__ inline real ls_iterate(int ne, real g1, real g2, real jr, real jv, re
   return alpha;
 }
 
+// ILQG_NT_REPLAY: leave a Newton loop once its state repeats.  An iteration
+// computes its search direction, line search, cost, gradient, active set and
+// factor from (qacc, M qacc, jar) and values fixed for the solve (qM, J, D,
+// aref, qfrc_smooth, qacc_smooth).  When an update leaves every word of those
+// three unchanged and the iteration passes the exit tests, the next iteration
+// has the same inputs: the same alpha != 0, the same update (unchanged
+// again), improvement exactly 0 -- not < tol at the FD sweep's tolerance 0 --
+// and the gradient that has just passed.  So it repeats bit for bit up to the
+// iteration cap and leaves the state as it is now: the loop may end here.  The
+// comparison is on bits (old word against new at the update, one ballot), so
+// -0 / +0 and NaN stay on the ordinary path.  Compiled into the FD
+// translation units only (rollout_body.h sets 0: at the model's tolerance a
+// frozen iteration already ends on improvement < tol), and taken only by
+// teams whose kernel set Team.replay (ILQG_NT_REPLAY in the environment, read
+// by the host; 0 = every iteration runs, the same records).
+#ifndef ILQG_NT_REPLAY
+#define ILQG_NT_REPLAY 1
+#endif
+constexpr bool NT_REPLAY = ILQG_NT_REPLAY != 0;
+__device__ __forceinline__ bool same_bits(double a, double b) {
+  return __double_as_longlong(a) == __double_as_longlong(b);
+}
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_int(a) == __float_as_int(b); }
+
 __device__ inline void solver_newton(const auto& m, const auto& L, const auto& C, const Team& T,
                                      int maxiter, real tol) {
   constexpr int NVC = nv_const<std::remove_cvref_t<decltype(m)>>();
@@ -2837,11 +2866,23 @@ __device__ inline void solver_newton(const auto& m, const auto& L, const auto& C
     STAMP(16);
     const real alpha = bc[3];
     if (alpha == 0) break;
+    // (ILQG_NT_REPLAY) same: this lane's words of qacc, Ma and jar kept their bits
+    const bool replay = NT_REPLAY && T.replay && T.nt == TEAM_SIZE;
+    bool same = true;
     FOR_T(j, nv) {
-      qacc[j] += alpha * search[j];
-      Ma[j] += alpha * Mv[j];
+      const real q0 = qacc[j], a0 = Ma[j];
+      const real q1 = q0 + alpha * search[j], a1 = a0 + alpha * Mv[j];
+      qacc[j] = q1;
+      Ma[j] = a1;
+      if (NT_REPLAY) same = same && same_bits(q0, q1) && same_bits(a0, a1);
     }
-    FOR_T(i, ne) jar[i] += alpha * Jv[i];
+    FOR_T(i, ne) {
+      const real j0 = jar[i];
+      const real j1 = j0 + alpha * Jv[i];
+      jar[i] = j1;
+      if (NT_REPLAY) same = same && same_bits(j0, j1);
+    }
+    const bool frozen = replay && __ballot(!same) == 0;
     TSYNC();
     iter++;
 #ifdef ILQG_STAMPS
@@ -2860,6 +2901,11 @@ __device__ inline void solver_newton(const auto& m, const auto& L, const auto& C
     STAMP(18);
     cost = c2;
     if (improvement < tol || gradient < tol) break;
+    if (frozen) {  // ILQG_NT_REPLAY: every iteration up to the cap repeats this one
+      CNT_ADD(10, (unsigned long long)(maxiter - iter));
+      iter = maxiter;
+      break;
+    }
     // the factor is a function of (qM, J, D, efc_state) alone: rebuilt only
     // when some row's state changed since it was computed (the same bits)
     if (chg) hessian_factor(m, L, C, T, H);
@@ -3325,11 +3371,20 @@ __device__ inline void fwd_constraint_u(const auto& m, const auto& L, const auto
     }
     STAMP(16);
     if (__ballot(alpha == 0) != 0) break;  // uniform
+    // (ILQG_NT_REPLAY) same: qacc, Ma and this lane's jar kept their bits
+    bool same = true;
     sfor<0, NV>(SLAM(jj) {
-      qacc[SK(jj)] += alpha * sv[SK(jj)];
-      Ma[SK(jj)] += alpha * Mv[SK(jj)];
+      const real q1 = qacc[SK(jj)] + alpha * sv[SK(jj)], a1 = Ma[SK(jj)] + alpha * Mv[SK(jj)];
+      if constexpr (NT_REPLAY) same = same && same_bits(qacc[SK(jj)], q1) && same_bits(Ma[SK(jj)], a1);
+      qacc[SK(jj)] = q1;
+      Ma[SK(jj)] = a1;
     });
-    jr += alpha * jv;
+    {
+      const real j1 = jr + alpha * jv;
+      if constexpr (NT_REPLAY) same = same && same_bits(jr, j1);
+      jr = j1;
+    }
+    const bool frozen = NT_REPLAY && T.replay && __ballot(!same) == 0;
     iter++;
     CNT_ADD(8, 1ull);
     STAMP(17);
@@ -3348,6 +3403,11 @@ __device__ inline void fwd_constraint_u(const auto& m, const auto& L, const auto
     const real gradient = scale * sqrt(dotu(grad, grad));
     STAMP(18);
     if (__ballot(improvement < tol || gradient < tol) != 0) break;
+    if (frozen) {  // ILQG_NT_REPLAY: every iteration up to the cap repeats this one
+      CNT_ADD(10, (unsigned long long)(maxiter - iter));
+      iter = maxiter;
+      break;
+    }
     // the factor is a function of (qM, J, D, active set) alone: rebuilt only
     // when the active set changed since it was computed (the same bits)
     if (mask != hmask) {
@@ -3647,11 +3707,21 @@ __device__ inline void fwd_constraint_fast(const auto& m, const auto& L, const a
     }
     STAMP(16);
     if (alpha == 0) break;
+    // (ILQG_NT_REPLAY) same: this lane's words of qacc and Ma and its jar kept their bits
+    bool same = true;
     FOR_T(j, nv) {
-      qacc[j] += alpha * search[j];
-      Ma[j] += alpha * Mv[j];
+      const real q0 = qacc[j], a0 = Ma[j];
+      const real q1 = q0 + alpha * search[j], a1 = a0 + alpha * Mv[j];
+      qacc[j] = q1;
+      Ma[j] = a1;
+      if (NT_REPLAY) same = same && same_bits(q0, q1) && same_bits(a0, a1);
     }
-    jr += alpha * jv;
+    {
+      const real j1 = jr + alpha * jv;
+      if (NT_REPLAY) same = same && same_bits(jr, j1);
+      jr = j1;
+    }
+    const bool frozen = NT_REPLAY && T.replay && __ballot(!same) == 0;
     TSYNC();
     iter++;
 #ifdef ILQG_STAMPS
@@ -3666,6 +3736,11 @@ __device__ inline void fwd_constraint_fast(const auto& m, const auto& L, const a
     const real gradient = scale * sqrt(tdot(grad, grad, nv));
     STAMP(18);
     if (improvement < tol || gradient < tol) break;
+    if (frozen) {  // ILQG_NT_REPLAY: every iteration up to the cap repeats this one
+      CNT_ADD(10, (unsigned long long)(maxiter - iter));
+      iter = maxiter;
+      break;
+    }
     if (mask != hmask) {
       hessian_build_fast(m, L, T, H, mask);
       cholesky_rows(nv, T.tid, H);

@@ -207,6 +207,10 @@ struct FdFused {
   int halves = 0;
   double* xq = nullptr;
   unsigned* pairc = nullptr;
+  // the FD teams' Newton loops end once their state repeats (dcoop_impl.h
+  // ILQG_NT_REPLAY; the host reads the environment's ILQG_NT_REPLAY once);
+  // 0 = every iteration runs.  The records are the same bits either way.
+  int nt_replay = 1;
 };
 // Plan the fused sweep's ticket order from the previous launch's per-item
 // durations (dur, all zero = no history: identity order).  Items of the first
@@ -239,6 +243,7 @@ struct FdArgs {
   double* deriv;
   int Ds;
   hipStream_t st;
+  int nt_replay = 1;  // as FdFused.nt_replay, a uniform argument of every kernel of the sweep
 };
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                  const coop::CoopAux& X, const FdArgs& a);

@@ -33,8 +33,9 @@ __device__ inline void fd_centre_body(const auto& m, const auto& L, const auto& 
 }
 
 template <class... SCH>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, SCH... cstride) {
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int replay, SCH... cstride) {
   Team T = make_team(L, C);
+  T.replay = replay;
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
@@ -43,11 +44,12 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevMod
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
 template <class SM, class SX, class... SCH>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, SCH... cstride) {
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c, int replay, SCH... cstride) {
   static constexpr WsLayout L = make_layout(SM{}, SX::npair);
   static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
   static constexpr SX X{};
   Team T = make_team(L, C);
+  T.replay = replay;
   SM m;
   stage_model_s(mg, L, C, T, m);
   fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
@@ -140,8 +142,9 @@ __device__ inline void fd_cols_body(const auto& m, const auto& L, const auto& C,
 }
 
 template <class... SCH>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, SCH... cstride) {
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel mg, WsLayout L, CoopLayout C, CoopAux Xg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int replay, SCH... cstride) {
   Team T = make_team(L, C);
+  T.replay = replay;
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
@@ -150,11 +153,12 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
 template <class SM, class SX, class... SCH>
-__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, SCH... cstride) {
+__global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg, TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds, int replay, SCH... cstride) {
   static constexpr WsLayout L = make_layout(SM{}, SX::npair);
   static constexpr CoopLayout C = make_coop_layout(SM{}, SX::npair);
   static constexpr SX X{};
   Team T = make_team(L, C);
+  T.replay = replay;
   SM m;
   stage_model_s(mg, L, C, T, m);
   fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
@@ -618,6 +622,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevMode
     return;
   }
   Team T = make_team(L, C);
+  T.replay = a.nt_replay;
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
@@ -641,6 +646,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
   Team T = make_team(L, C);
   T.iw = reinterpret_cast<int*>(lds + L.nd + C.nd);  // no image region
   T.ci = T.iw + L.ni;
+  T.replay = a.nt_replay;
   SM m;
   m.bind(mg.img, mg);
   fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
@@ -651,11 +657,11 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
 // reaches last, and gives the last copy of a shared function to, follows the
 // order of instantiation: left to the launchers' order of use,
 // k_fd_fused_coop grew by 10k instructions and 120 SGPR spills.
-template __global__ void k_fd_centre_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*);
-template __global__ void k_fd_cols_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int);
+template __global__ void k_fd_centre_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int);
+template __global__ void k_fd_cols_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int);
 template __global__ void k_fd_fused_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused);
-template __global__ void k_fd_centre_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int);
-template __global__ void k_fd_cols_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int);
+template __global__ void k_fd_centre_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int, int);
+template __global__ void k_fd_cols_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int, int);
 template __global__ void k_fd_fused_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused, int);
 
 // ---- the fused sweep's ticket schedule (launch_fd_plan) -----------------
@@ -808,11 +814,11 @@ static hipError_t fd_centre(const DevModel& m, const WsLayout& L, const CoopLayo
   hipError_t e = hipSuccess;
   if (for_static_model(m.static_id, [&](auto sm, auto sx) {
         e = launch(k_fd_centre_s<decltype(sm), decltype(sx), SCH...>, a.npts, TEAM, lds, a.st, m, a.tr, a.P,
-                   a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+                   a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, a.nt_replay, cs...);
       }))
     return e;
   return launch(k_fd_centre_coop<SCH...>, a.npts, TEAM, lds, a.st, m, L, C, X, a.tr, a.P, a.qfrc_applied,
-                a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+                a.xfrc_applied, a.cost, a.warm_c, a.cost_c, a.nt_replay, cs...);
 }
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                  const FdArgs& a) {
@@ -828,11 +834,11 @@ static hipError_t fd_cols(const DevModel& m, const WsLayout& L, const CoopLayout
   hipError_t e = hipSuccess;
   if (for_static_model(m.static_id, [&](auto sm, auto sx) {
         e = launch(k_fd_cols_s<decltype(sm), decltype(sx), SCH...>, blocks, TEAM, lds, a.st, m, a.tr, a.P,
-                   a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, cs...);
+                   a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, a.nt_replay, cs...);
       }))
     return e;
   return launch(k_fd_cols_coop<SCH...>, blocks, TEAM, lds, a.st, m, L, C, X, a.tr, a.P, a.qfrc_applied,
-                a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, cs...);
+                a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, a.nt_replay, cs...);
 }
 hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                const FdArgs& a) {

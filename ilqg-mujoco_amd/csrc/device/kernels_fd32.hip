@@ -48,6 +48,7 @@ __device__ inline Team make_team32(const WsLayout& L, const coop::CoopLayout& C)
   T.ci = T.iw + L.ni;
   T.tid = threadIdx.x & (TEAM32 - 1);
   T.nt = TEAM32;
+  T.replay = 0;
   return T;
 }
 
@@ -99,10 +100,12 @@ template <class MT, class... SCH>
 __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L, coop::CoopLayout C, coop::CoopAux X,
                                                         TrajDev tr, int P, const double* qfrc_applied,
                                                         const double* xfrc_applied, CostDev cost, double* warm_c,
-                                                        double* cost_c, SCH... cstride) {
+                                                        double* cost_c, int replay, SCH... cstride) {
   MT m;
   static_cast<DevModel&>(m) = mg;
   Team T = make_team32(L, C);
+  T.replay = replay;
+  STAMP_INIT();
   const int pt = blockIdx.x;
   if constexpr (sizeof...(SCH) > 0) cost = cost_at(cost, pt % P, (cstride, ...));
   load_state32(m, L, T, tr, pt, pt / P, qfrc_applied, xfrc_applied);
@@ -112,6 +115,7 @@ __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L,
   FOR_T(i, m.nv) warm_c[(size_t)pt * m.nv + i] = T.w[L.warm + i];
   // the centre cost on the fp32 state, as the perturbed costs below see it
   if (T.tid == 0) cost_c[pt] = step_cost32(m, cost, T.w + L.qpos, T.w + L.qvel, T.w + L.ctrl);
+  STAMP_FLUSH();
 }
 
 template <class MT, class... SCH>
@@ -119,10 +123,12 @@ __global__ __launch_bounds__(TEAM32) void k_fd_cols32(DevModel mg, WsLayout L, c
                                                       TrajDev tr, int P, const double* qfrc_applied,
                                                       const double* xfrc_applied, CostDev cost, const double* warm_c,
                                                       const double* cost_c, double* deriv, int Ds, float eps,
-                                                      SCH... cstride) {
+                                                      int replay, SCH... cstride) {
   MT m;
   static_cast<DevModel&>(m) = mg;
   Team T = make_team32(L, C);
+  T.replay = replay;
+  STAMP_INIT();
   const int nv = m.nv, nu = m.nu;
   const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   const int ncol = nctrl + 2 * nv;
@@ -196,6 +202,7 @@ __global__ __launch_bounds__(TEAM32) void k_fd_cols32(DevModel mg, WsLayout L, c
     else if (kind == 1) dr[nv * nv + i + j * nv] = v;
     else dr[i + j * nv] = v;
   }
+  STAMP_FLUSH();
 }
 
 }  // namespace
@@ -215,10 +222,10 @@ static hipError_t fd_sweep32(const DevModel& m, const WsLayout& L, const coop::C
   return for_model_type<DevModelNV>(m, [&](auto mt) {
     using MT = typename decltype(mt)::type;
     hipError_t e = launch(k_fd_centre32<MT, SCH...>, a.npts, TEAM32, lds, a.st, m, L, C, X, a.tr, a.P,
-                          a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, cs...);
+                          a.qfrc_applied, a.xfrc_applied, a.cost, a.warm_c, a.cost_c, a.nt_replay, cs...);
     if (e != hipSuccess) return e;
     return launch(k_fd_cols32<MT, SCH...>, (unsigned)blocks, TEAM32, lds, a.st, m, L, C, X, a.tr, a.P,
-                  a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, eps, cs...);
+                  a.qfrc_applied, a.xfrc_applied, a.cost, warm_c, cost_c, a.deriv, a.Ds, eps, a.nt_replay, cs...);
   });
 }
 
@@ -229,3 +236,20 @@ hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop:
 }
 
 }  // namespace ilqg
+
+#ifdef ILQG_STAMPS
+// the fp32 kernels' copy of the Newton counters (dcoop_impl.h): iterations
+// executed, solves, iterations the replay exit skipped (ILQG_NT_REPLAY)
+extern "C" int ilqg_debug_newton_fd32(unsigned long long* out3, int reset) {
+  if (hipMemcpyFromSymbol(&out3[0], HIP_SYMBOL(ilqg::coopf::g_newton_iters), 8) != hipSuccess) return 3;
+  if (hipMemcpyFromSymbol(&out3[1], HIP_SYMBOL(ilqg::coopf::g_newton_calls), 8) != hipSuccess) return 3;
+  if (hipMemcpyFromSymbol(&out3[2], HIP_SYMBOL(ilqg::coopf::g_newton_skipped), 8) != hipSuccess) return 3;
+  if (reset) {
+    const unsigned long long z = 0;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coopf::g_newton_iters), &z, 8);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coopf::g_newton_calls), &z, 8);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(ilqg::coopf::g_newton_skipped), &z, 8);
+  }
+  return 0;
+}
+#endif

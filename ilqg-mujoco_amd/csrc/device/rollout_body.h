@@ -22,6 +22,11 @@
 #ifndef ILQG_LS_TREE
 #define ILQG_LS_TREE 0
 #endif
+// (the Newton loops' replay exit, dcoop_impl.h: a frozen iteration ends these
+// solves on improvement < tol already, and the kernel is sensitive to code size)
+#ifndef ILQG_NT_REPLAY
+#define ILQG_NT_REPLAY 0
+#endif
 #include "coop_common.h"
 
 namespace ilqg {

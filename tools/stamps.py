@@ -67,6 +67,10 @@ for what, fn, rd, rls in (("rollout (1 seed)", g.forward_pass, L.ilqg_debug_stam
     if acc[45]:
         print(f"   Newton (all workgroups): {acc[45]} solves, {acc[44]} iterations, "
               f"{acc[44] / acc[45]:.2f} iterations per solve")
+        if what == "fd sweep":
+            # ILQG_NT_REPLAY: executed + skipped is the count ILQG_NT_REPLAY=0 executes
+            print(f"   Newton iterations executed {acc[44]}, skipped by the replay exit {acc[60]} "
+                  f"(ILQG_NT_REPLAY={os.environ.get('ILQG_NT_REPLAY', '1')}), sum {acc[44] + acc[60]}")
     if acc[46]:
         print(f"   block 0 lifetime: {acc[46] / 100:.0f} us realtime, {acc[47]} memtime ticks "
               f"-> shader clock {acc[47] / (acc[46] / 100) :.0f} MHz; the stamps attribute "
@@ -80,6 +84,17 @@ for what, fn, rd, rls in (("rollout (1 seed)", g.forward_pass, L.ilqg_debug_stam
         for i in W2:
             if cnt[i]:
                 print(f"  {W2[i]:24s} calls {cnt[i]:6d}  cycles/call {acc[i]/cnt[i]:9.0f}  share {acc[i]/tot2:6.1%}")
+
+if m.nq != m.nv:
+    # the fp32 FD sweep (kernels_fd32.hip keeps its own copy of the Newton counters)
+    nt = (ctypes.c_ulonglong * 3)()
+    g.set_fd_precision("f32")
+    L.ilqg_debug_newton_fd32(nt, 1)
+    g.fd_sweep(); g.synchronize()
+    L.ilqg_debug_newton_fd32(nt, 1)
+    g.set_fd_precision("f64")
+    print(f"== fp32 fd sweep: Newton (all workgroups): {nt[1]} solves, iterations executed {nt[0]}, skipped by the "
+          f"replay exit {nt[2]} (ILQG_NT_REPLAY={os.environ.get('ILQG_NT_REPLAY', '1')}), sum {nt[0] + nt[2]}")
 
 # ilqg_backward on the hopper: the one-wave recursion (riccati.h)
 BN = ["A Vs col, T1, v(prev), w", "B T3, Mm, col", "C LDLT, k, K col, ABK, y", "D T4, T6", "E Vn, z, record"]
