@@ -282,6 +282,14 @@ struct ilqg_solver {
   std::vector<hipEvent_t> pipe_ev;
   DevBuf carry[5];  // the chunked rollout's state between launches, [S][...]
   bool pipe_ready = false;  // pipe_setup done (fd_stream, pipe_ev, carry)
+  // ilqg_solver_shift_horizon: new point n per seed, [S][...], which the move
+  // kernel writes and the tail's passive rollout starts from (first call allocates)
+  DevBuf shift_carry[5];
+  // its tail, compact: points n .. 0 of every seed as a trajectory of n + 1
+  // points, [S][n + 1][...], and their FD records [S][n + 1][Dp] -- one rollout
+  // launch and one sweep launch for all seeds, then stored into the resident
+  // arrays (sized for n = N)
+  DevBuf shift_tail[5], shift_rec;
   // seed groups (ilqg_solver_set_groups): the seeds as G contiguous ranges,
   // software-pipelined.  Group g has a rollout stream (CU-masked to an XCD of
   // its own: one rollout workgroup per CU) and a sweep stream (every CU but the
@@ -1372,25 +1380,26 @@ int ilqg_fd_sweep(ilqg_solver* s) {
   return ILQG_OK;
 }
 
+// the unfused sweep of the solver's FD precision over the points `a` describes
+static hipError_t fd_points_launch(ilqg_solver* s, const FdArgs& a) {
+  const ilqg_model* m = s->model;
+  if (s->fdprec == ILQG_FD_F32) return launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, a, ILQG_FD32_EPS);
+  hipError_t e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, a);
+  if (e == hipSuccess) e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, a);
+  return e;
+}
+
 // calcMJDerivatives at points p0 .. p0 + np - 1 of every seed: the share of
 // one rank in a point-sharded sweep (a single seed's FD sweep spread over
 // GPUs; the records are then all-gathered and every rank runs the recursion).
 // The unfused kernels of the solver's FD precision, one launch pair per seed;
 // the same records the whole-trajectory sweep writes.
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st) {
-  const ilqg_model* m = s->model;
   // the kernels' seed index pt / P is 0 for every point of the range, and their
   // point index pt % P counts from p0: the cost schedule is passed from row p0 on
   constexpr int kOneSeed = 1 << 30;
   for (int sd = 0; sd < s->S; sd++) {
-    const FdArgs a = fd_args(s, sd, p0, np, kOneSeed, st);
-    hipError_t e;
-    if (s->fdprec == ILQG_FD_F32) {
-      e = launch_fd_sweep_f32(m->dm, m->Lc, m->C, m->X, a, ILQG_FD32_EPS);
-    } else {
-      e = launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, a);
-      if (e == hipSuccess) e = launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, a);
-    }
+    const hipError_t e = fd_points_launch(s, fd_args(s, sd, p0, np, kOneSeed, st));
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1402,6 +1411,89 @@ int ilqg_fd_sweep_range(ilqg_solver* s, int p0, int np) {
   if (!np) return ILQG_OK;
   s->grp_join = true;
   HIPCHK(s->timed(3, [&] { return fd_range_launch(s, p0, np, s->stream); }));
+  return ILQG_OK;
+}
+
+// The receding-horizon tick of the nominal: five launches on the solver's
+// stream and nothing else.
+//  - the in-place move (k_shift_horizon), which also zeroes the gains below n
+//    and writes dinit = new point N and shift_carry = new point n;
+//  - the tail as a passive rollout of horizon n from shift_carry into the
+//    compact trajectory shift_tail, [S][n + 1]: the constructor's launch with
+//    another start and length, so the bits are ilqg_solver_init's and
+//    ilqg_step_batch's (its point n is new point n again; passive: no control
+//    law, no clamp, no cost row, no cost out);
+//  - the FD records of the compact trajectory through fd_points_launch, the
+//    launch fd_range_launch makes per seed -- here once for every seed, P =
+//    n + 1 points per seed, so seed pt / P carries its forces and point pt % P
+//    its cost row.  (Measured: fd_range_launch(s, 0, n) itself, S launch pairs
+//    of one FD evaluation's latency each, took 1.4 ms of a 1.5 ms tick on the
+//    bench workload, dealt over four streams still 1.1 ms: DESIGN.md.)  Point
+//    n's record is computed once more and dropped;
+//  - k_shift_store: points n-1 .. 0 of shift_tail and their records into the
+//    resident trajectory and records.
+int ilqg_solver_shift_horizon(ilqg_solver* s, int n, int tail) {
+  if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
+  if (n < 1 || n > s->P - 1) return fail(ILQG_ERR_ARG, "horizon shift: n must be in 1 .. horizon");
+  if (tail != ILQG_TAIL_HOLD) return fail(ILQG_ERR_ARG, "horizon shift: the only tail mode is ILQG_TAIL_HOLD");
+  const ilqg_model* m = s->model;
+  const HostModel& h = m->host;
+  const int fld[5] = {1, h.nq, h.nv, h.nv, h.nu};
+  const size_t S = s->S, P = s->P;
+  // first call: the buffers, zeroed on the solver's stream (DevBuf::alloc zeroes
+  // on the null stream, which does not order with it: the launches below would
+  // race with that memset)
+  auto lazy = [&](DevBuf& b, size_t bytes) -> hipError_t {
+    if (b.p) return hipSuccess;
+    hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) { b.p = nullptr; return e; }
+    b.n = bytes;
+    return hipMemsetAsync(b.p, 0, bytes, s->stream);
+  };
+  for (int f = 0; f < 5; f++) {
+    HIPCHK(lazy(s->shift_carry[f], S * fld[f] * 8));
+    HIPCHK(lazy(s->shift_tail[f], S * P * fld[f] * 8));
+  }
+  HIPCHK(lazy(s->shift_rec, S * P * s->Dp * 8));
+  s->grp_join = true;
+  ShiftArgs a{};
+  for (int f = 0; f < 5; f++) {
+    a.arr[f] = s->traj[f].as<double>();
+    a.w[f] = fld[f];
+    a.dinit[f] = s->dinit[f].as<double>();
+    a.carry[f] = s->shift_carry[f].as<double>();
+    a.tail[f] = s->shift_tail[f].as<double>();
+  }
+  a.arr[ShiftArgs::ARR_K] = s->K.as<double>();
+  a.w[ShiftArgs::ARR_K] = h.nu * s->nx;
+  a.arr[ShiftArgs::ARR_k] = s->k.as<double>();
+  a.w[ShiftArgs::ARR_k] = h.nu;
+  a.arr[ShiftArgs::ARR_DERIV] = s->deriv.as<double>();
+  a.w[ShiftArgs::ARR_DERIV] = s->Dp;
+  a.tail[5] = s->shift_rec.as<double>();
+  a.S = s->S;
+  a.P = s->P;
+  a.n = n;
+  HIPCHK(s->timed(1, [&] { return launch_shift_horizon(a, s->stream); }));
+  const TrajDev tl = s->tview(s->shift_tail);
+  HIPCHK(s->timed(0, [&] {
+    return launch_rollout_coop(m->dm, m->Lc, m->C, m->X,
+                               RollArgs{s->S, 1, n + 1, tl, tl, 0, s->K.as<double>(), s->k.as<double>(), nullptr,
+                                        s->tview(s->shift_carry), s->qfrc_applied.as<double>(),
+                                        s->xfrc_applied.as<double>(), 1, s->cview0(), nullptr, s->stream,
+                                        RollChunk{}, 0});
+  }));
+  HIPCHK(s->timed(3, [&] {
+    return fd_points_launch(s, FdArgs{tl, s->S * (n + 1), n + 1, s->qfrc_applied.as<double>(),
+                                      s->xfrc_applied.as<double>(), s->cview(0), s->cstride(),
+                                      s->warm_c.as<double>(), s->cost_c.as<double>(), s->shift_rec.as<double>(),
+                                      s->Dp, s->stream, s->nt_replay});
+  }));
+  HIPCHK(s->timed(1, [&] { return launch_shift_store(a, s->stream); }));
+  // stale by construction: the boxed pass's report, the nominal's cost (in
+  // stream, unlike reg_invalidate: nothing here waits for the device)
+  s->cl_valid = false;
+  if (s->reg_on) HIPCHK(hipMemsetAsync(s->reg_valid.p, 0, s->reg_valid.n, s->stream));
   return ILQG_OK;
 }
 

@@ -169,6 +169,29 @@ hipError_t launch_backward_mfma(const DevModel& m, int S, int P, double mu, cons
 size_t backward_mfma_lds_bytes(int nv, int nu);
 bool backward_mfma_supported(int nv, int nu);
 
+// Horizon shift (ilqg_solver_shift_horizon; kernels_shift.hip).
+// k_shift_horizon: per seed and per-point array, point p takes point p - n for
+// p = N .. n, in place.  arr[i]: [S][P][w[i]] doubles -- the trajectory's five
+// fields (TrajDev order), then K, k and the FD records at their padded stride.
+// Behind the move: K and k zero below n; dinit[f][s] = new point N and
+// carry[f][s] = new point n of field f, the state the tail's passive rollout
+// starts from.
+// k_shift_store: the tail, computed compactly -- tail[f]: [S][n + 1][w[f]] for
+// the five fields (a trajectory of n + 1 points per seed, its point n = new
+// point n), tail[5]: their FD records [S][n + 1][w[ARR_DERIV]] -- into points
+// n-1 .. 0 of the resident trajectory and records.
+struct ShiftArgs {
+  static constexpr int NARR = 8, ARR_K = 5, ARR_k = 6, ARR_DERIV = 7, NTAIL = 6;
+  double* arr[NARR];
+  int w[NARR];
+  double* dinit[5];
+  double* carry[5];
+  const double* tail[NTAIL];
+  int S, P, n;  // 1 <= n <= P - 1
+};
+hipError_t launch_shift_horizon(const ShiftArgs& a, hipStream_t st);
+hipError_t launch_shift_store(const ShiftArgs& a, hipStream_t st);
+
 // fused FD sweep + streamed backward pass (kernels_fd.hip)
 struct FdFused {
   TrajDev tr;

@@ -74,7 +74,9 @@ EXPORTS = [
     "ilqg_solver_set_recursion", "ilqg_solver_get_expected",
     "ilqg_solver_set_regularization", "ilqg_solver_get_regularization", "ilqg_solver_get_reg_state",
     "ilqg_solver_set_reg_mu", "ilqg_solver_get_reg_trace",
+    "ilqg_solver_shift_horizon",
 ]
+TAIL_MODES = {"hold": 0}  # ILQG_TAIL_HOLD
 REG_MAXRETRY, REG_MAXTRACE, REG_TRACE = 16, 1024, 8
 REG_TRACE_FIELDS = ("cost_nom", "cost_best", "chosen", "expected", "mu_before", "mu_accept", "mu_backward", "code")
 
@@ -133,6 +135,8 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(LIB_PATH)
         L.ilqg_last_error.restype = ctypes.c_char_p
         L.ilqg_solver_stream.restype = ctypes.c_void_p
+        L.ilqg_solver_shift_horizon.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.ilqg_solver_shift_horizon.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -607,6 +611,20 @@ class ILQR:
         if n >= 1 and new_rows.shape[0] != n:
             raise IlqgError(f"shift_cost_schedule: {n} steps need {n} new rows, got {new_rows.shape[0]}")
         _check(lib().ilqg_solver_shift_cost_schedule(self._h, n, _ptr(new_rows)), "shift_cost_schedule")
+
+    def shift_horizon(self, n: int = 1, tail="hold"):
+        """the receding-horizon tick of the nominal (ilqg_solver_shift_horizon;
+        the reference reuses dArray unshifted): per seed, point p takes the
+        trajectory entry, the gains and the FD record of point p - n, in place on
+        the device; points n-1 .. 0 continue the rollout past the old terminal
+        point holding its control, with zero gains and freshly swept records;
+        dinit becomes the new point N.  Enqueued on the solver's stream, no
+        host sync.  With a cost schedule: shift_cost_schedule first."""
+        if isinstance(tail, str):
+            if tail not in TAIL_MODES:
+                raise IlqgError(f"shift_horizon: tail must be one of {sorted(TAIL_MODES)}")
+            tail = TAIL_MODES[tail]
+        _check(lib().ilqg_solver_shift_horizon(self._h, int(n), int(tail)), "shift_horizon")
 
     def set_groups(self, ngroups: int):
         """seed groups (ilqg_solver_set_groups): iterate() software-pipelines

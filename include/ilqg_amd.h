@@ -288,6 +288,48 @@ int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled);
    advancing clock by itself.  ILQG_ERR_ARG while the schedule is off, for
    n < 1 or n > N+1, and for new_rows NULL or non-finite.  Synchronises. */
 int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows);
+/* Horizon shift: the receding-horizon tick of the nominal trajectory, the gains
+   and the FD records, on the device.  The reference has no counterpart: its
+   driver reuses dArray unshifted as the next nominal.  Per seed,
+   with points indexed as everywhere (p = N now, p = 0 terminal):
+   1. move: for p = N .. n every per-point array takes the entry of old point
+      p - n -- the trajectory's five fields, K[p] and k[p], the FD record p (its
+      whole padded slot) -- in place: the pointers ilqg_solver_device_traj,
+      ilqg_solver_device_deriv and ilqg_solver_device_costs hand out stay valid;
+   2. tail: points n-1 .. 0 continue the rollout past the old terminal point
+      holding its control: from new point n one mj_step with the stored ctrl[n]
+      (forwardPass after storing a point, inc/ilqr.h:127-128), the resulting
+      time, qpos, qvel, qacc_warmstart stored as point n-1 with ctrl[n-1] =
+      ctrl[n], and so on down to point 0.  The seed's qfrc_applied /
+      xfrc_applied apply; control limits do not re-clamp the held control (it
+      was stored clamped).  K[p] = 0 and k[p] = 0 for p < n;
+   3. tail records: the FD records of points 0 .. n-1 are swept behind the
+      tail on the same stream, by the kernels of ilqg_fd_sweep_range(s, 0, n)
+      launched once for every seed (the same records): the FD precision that
+      is set and the cost rows in force at that moment -- with a schedule
+      the tick is ilqg_solver_shift_cost_schedule, then this call, and a moved
+      record is still the record of its point under its row;
+   4. dinit takes new point N, the nominal's prediction of "now", so that
+      ilqg_iterate can follow with no host call; a later ilqg_solver_set_dinit
+      overrides it as ever.
+   Enqueued on the solver's stream: no synchronisation, nothing copied to or
+   from the host (the first call on a solver allocates the tail's staging
+   buffers, a second trajectory and record array, zeroed in stream).
+   Seed groups wait for it as for ilqg_fd_sweep_range; under
+   ilqg_forward_sharded every rank shifts identically and sweeps the n tail
+   points itself.  Stale by construction afterwards: ilqg_solver_get_value and
+   ilqg_solver_get_costs keep the last pass's values, ilqg_solver_get_clamped
+   reads 0 until the next boxed pass, and in the regularisation mode the nominal
+   cost is invalid (mu, dmu, status and the trace are untouched; the shifted
+   nominal's cost is not recomputed on the device).  With ilqg_solver_set_timing
+   the move and the tail's store count under index 1, the tail's rollout under
+   0, the tail sweep under 3.
+   ILQG_ERR_ARG: s NULL or not initialised, n < 1, n > N, tail not
+   ILQG_TAIL_HOLD (the only tail built; a zero-control tail is not).  Composes
+   with both layouts and recursions, limits, the cost schedule, fp32 FD, the
+   MFMA engine and seed groups, and changes no refusal. */
+#define ILQG_TAIL_HOLD 0
+int ilqg_solver_shift_horizon(ilqg_solver* s, int n, int tail);
 /* Recursion mode.  REFERENCE (default): the backward step of inc/ilqr.h:157-174
    as the reference wrote it (outer products of the FD cost gradients for
    Hessians, mu added to V and kept, factors of 2: SURVEY.md Appendix A Q13,
