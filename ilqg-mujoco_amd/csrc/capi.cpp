@@ -82,6 +82,13 @@ int check_device_support(const HostModel& m, bool solver, std::string& why) {
       why = "stiffness on ball/free joints is not supported";
       return ILQG_ERR_UNSUPPORTED;
     }
+  // limit rows are built for slide and hinge joints only: a limited ball joint
+  // would be simulated without its limit, so it is refused
+  for (int j = 0; j < m.njnt; j++)
+    if (m.jnt_type[j] == 1 && m.jnt_limited[j]) {
+      why = "a limited ball joint (joint " + std::to_string(j) + ") is not supported: ball-joint limits are not simulated";
+      return ILQG_ERR_UNSUPPORTED;
+    }
   auto power_ok = [](double p) { return p == (double)(int)p && p >= 1 && p <= 8; };
   for (int j = 0; j < m.njnt; j++)
     if (!power_ok(m.jnt_solimp[5 * j + 4])) { why = "solimp power must be an integer in [1,8]"; return ILQG_ERR_UNSUPPORTED; }

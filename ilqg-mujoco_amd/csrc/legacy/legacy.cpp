@@ -22,6 +22,7 @@
 #include "ilqg_model_fields.h"
 #include "mjderivative.h"
 #include "mujoco/mujoco.h"
+#include "quat_host.h"
 #include "update.h"
 #include "util.h"
 
@@ -220,29 +221,14 @@ void mju_error_s(const char* msg, const char* text) {
   mju_error(buf);
 }
 
-// MuJoCo 2.0 mju_quatIntegrate: rotate quat by vel*scale (axis-angle), host libm
+// MuJoCo 2.0 mju_quatIntegrate: rotate quat by vel*scale (axis-angle).  The
+// operation sequence of the device's quat_integrate (csrc/device/dphys.h),
+// restated for the host in quat_host.h: fdlibm sin / cos, the reciprocal of
+// the norm, a quaternion within mjMINVAL of unit length left unnormalised -- so
+// host_cost_columns perturbs a ball or free quaternion to the doubles the FD
+// kernels perturb it to, not merely to within rounding of them.
 void mju_quatIntegrate(mjtNum* quat, const mjtNum* vel, mjtNum scale) {
-  mjtNum ax[3] = {vel[0], vel[1], vel[2]};
-  mjtNum nrm = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-  if (nrm < mjMINVAL) {
-    ax[0] = 1; ax[1] = 0; ax[2] = 0;
-  } else {
-    ax[0] /= nrm; ax[1] /= nrm; ax[2] /= nrm;
-  }
-  const mjtNum ang = scale * nrm;
-  const mjtNum s = std::sin(ang * 0.5);
-  mjtNum qr[4] = {std::cos(ang * 0.5), ax[0] * s, ax[1] * s, ax[2] * s};
-  mjtNum qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
-  if (qn < mjMINVAL) {
-    quat[0] = 1; quat[1] = quat[2] = quat[3] = 0;
-  } else {
-    for (int i = 0; i < 4; i++) quat[i] /= qn;
-  }
-  mjtNum q[4] = {quat[0] * qr[0] - quat[1] * qr[1] - quat[2] * qr[2] - quat[3] * qr[3],
-                 quat[0] * qr[1] + quat[1] * qr[0] + quat[2] * qr[3] - quat[3] * qr[2],
-                 quat[0] * qr[2] - quat[1] * qr[3] + quat[2] * qr[0] + quat[3] * qr[1],
-                 quat[0] * qr[3] + quat[1] * qr[2] - quat[2] * qr[1] + quat[3] * qr[0]};
-  for (int i = 0; i < 4; i++) quat[i] = q[i];
+  ilqg_legacy::hostq::quat_integrate(quat, vel, scale);
 }
 
 }  // extern "C"

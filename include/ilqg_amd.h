@@ -510,7 +510,7 @@ int ilqg_solver_get_groups(ilqg_solver* s, int* ngroups, int* rollout_cus);
    groups every launch is on that stream anyway and this is a no-op */
 int ilqg_solver_join_stream(ilqg_solver* s);
 /* sha256 prefix (16 hex digits) of the sources this library was built from
-   (csrc/**, Makefile; the same digest as ilqg_amd.source_sha()): the host
+   (all of csrc, Makefile; the same digest as ilqg_amd.source_sha()): the host
    refuses a library whose digest differs from the sources beside it */
 const char* ilqg_source_sha(void);
 /* device pointer to the per-seed selected-candidate cost (nseed doubles), for

@@ -12,11 +12,29 @@
 //                                      was set to X first (inc/ilqr.h:65,166); same output
 //   legacy_members model.xml mutate    one iterate() of a subclass whose initV changes
 //                                      dArray[N/2] after the default; same output
+// and three modes that are not tied to the pendulum's nv = 2, nu = 1 (any model;
+// every number read or printed is a C hex float, so nothing is rounded on the way):
+//   legacy_members - quat seed count   mju_quatIntegrate on `count` seeded cases; prints
+//                                      "case quat[4] vel[3] scale" and "out quat[4]" rows (CPU)
+//   legacy_members model.xml costcols cases.txt
+//                                      host_cost_columns at every state of the file with the
+//                                      file's cost descriptor as the host callback; "g" rows (CPU)
+//   legacy_members model.xml fd cases.txt [--device-cost]
+//                                      calcMJDerivatives at every state with the host callback,
+//                                      or with the descriptor registered for it; "deriv" rows (GPU)
+// cases.txt: rows "wq|tq|lq|wv|tv|lv|wu|tu|lu values..." (absent rows are zero) and rows
+// "state time qpos[nq] qvel[nv] warm[nv] ctrl[nu]".
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "differentiator.h"
+#include "ilqg_amd.h"
+#include "ilqg_legacy.h"
 #include "ilqr.h"
 #include "mjderivative.h"
 #include "mujoco/mujoco.h"
@@ -200,17 +218,169 @@ int mu(mjModel* m, mjData* d0, mjtNum value, int iters) {
   dump(m, il);
   return 0;
 }
+
+// ---- modes for any model ----
+// splitmix64: the seeded cases of the quat mode
+uint64_t g_rng = 0;
+uint64_t next64() {
+  uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+double uniform(double lo, double hi) { return lo + (hi - lo) * ((next64() >> 11) * (1.0 / 9007199254740992.0)); }
+
+// a third exactly the identity, the rest seeded unit quaternions: as numpy-style
+// rounding leaves them (|norm - 1| of a few 1e-16), scaled by 1 +- a few 1e-16
+// (inside normalize4's window of 1e-15 or just around it), or denormalised by 1e-12;
+// each with +-1e-6 e_k and with general velocities at scales 0.002 and 1
+int quat_cases(uint64_t seed, int count) {
+  g_rng = seed;
+  for (int c = 0; c < count; c++) {
+    mjtNum q[4] = {1, 0, 0, 0};
+    const int kind = c % 6;  // 0, 1: identity
+    if (kind >= 2) {
+      mjtNum n = 0;
+      for (int i = 0; i < 4; i++) { q[i] = uniform(-1, 1); n += q[i] * q[i]; }
+      n = std::sqrt(n);
+      for (int i = 0; i < 4; i++) q[i] /= n;
+      const mjtNum f = kind == 3 ? 1 + uniform(1e-16, 1e-15) : kind == 4 ? 1 - uniform(1e-16, 1e-15)
+                       : kind == 5 ? 1 + (c % 12 == 5 ? 1e-12 : -1e-12) : 1.0;
+      for (int i = 0; i < 4; i++) q[i] *= f;
+    }
+    mjtNum vel[3] = {0, 0, 0}, scale = 1;
+    const int vk = (c / 6) % 8;
+    if (vk < 6) {
+      vel[vk % 3] = vk < 3 ? 1e-6 : -1e-6;  // the FD sweep's own perturbation
+    } else {
+      for (int i = 0; i < 3; i++) vel[i] = uniform(-4, 4);
+      scale = vk == 6 ? 0.002 : 1.0;
+    }
+    printf("case %a %a %a %a %a %a %a %a\n", q[0], q[1], q[2], q[3], vel[0], vel[1], vel[2], scale);
+    mju_quatIntegrate(q, vel, scale);
+    hex("out", q, 4);
+  }
+  return 0;
+}
+
+struct Cases {
+  std::vector<mjtNum> a[9];  // wq tq lq wv tv lv wu tu lu
+  std::vector<std::vector<mjtNum>> states;
+};
+Cases g_cases;
+int g_nq = 0, g_nv = 0, g_nu = 0;
+
+// the descriptor cost in the oracle's expression order (per entry: the quadratic
+// term when its weight is not zero, then the linear term when its weight is not
+// zero; qpos, qvel, ctrl; index ascending)
+mjtNum desc_terms(mjtNum c, const mjtNum* x, const mjtNum* w, const mjtNum* t, const mjtNum* l, int n) {
+  for (int i = 0; i < n; i++) {
+    if (w[i] != 0) {
+      mjtNum dx = x[i] - t[i];
+      c += w[i] * dx * dx;
+    }
+    if (l[i] != 0) c += l[i] * x[i];
+  }
+  return c;
+}
+mjtNum descCost(const mjData* d) {
+  const Cases& C = g_cases;
+  mjtNum s = 0;
+  s = desc_terms(s, d->qpos, C.a[0].data(), C.a[1].data(), C.a[2].data(), g_nq);
+  s = desc_terms(s, d->qvel, C.a[3].data(), C.a[4].data(), C.a[5].data(), g_nv);
+  s = desc_terms(s, d->ctrl, C.a[6].data(), C.a[7].data(), C.a[8].data(), g_nu);
+  return s;
+}
+
+bool read_cases(const char* path, const mjModel* m) {
+  static const char* tags[9] = {"wq", "tq", "lq", "wv", "tv", "lv", "wu", "tu", "lu"};
+  const int len[9] = {m->nq, m->nq, m->nq, m->nv, m->nv, m->nv, m->nu, m->nu, m->nu};
+  g_nq = m->nq; g_nv = m->nv; g_nu = m->nu;
+  for (int i = 0; i < 9; i++) g_cases.a[i].assign(len[i], 0.0);
+  FILE* f = fopen(path, "r");
+  if (!f) return false;
+  char tag[16];
+  const size_t nstate = 1 + (size_t)m->nq + 2 * (size_t)m->nv + m->nu;
+  while (fscanf(f, "%15s", tag) == 1) {
+    std::vector<mjtNum>* dst = nullptr;
+    size_t want = nstate;
+    for (int i = 0; i < 9; i++)
+      if (!strcmp(tag, tags[i])) { dst = &g_cases.a[i]; want = (size_t)len[i]; }
+    if (!dst) {
+      if (strcmp(tag, "state")) { fclose(f); return false; }
+      g_cases.states.emplace_back();
+      dst = &g_cases.states.back();
+    }
+    dst->assign(want, 0.0);
+    for (size_t k = 0; k < want; k++) {
+      char tok[64];
+      if (fscanf(f, "%63s", tok) != 1) { fclose(f); return false; }
+      (*dst)[k] = strtod(tok, nullptr);
+    }
+  }
+  fclose(f);
+  return !g_cases.states.empty();
+}
+
+void load_state(const mjModel* m, mjData* d, const std::vector<mjtNum>& s) {
+  const mjtNum* p = s.data();
+  d->time = *p++;
+  mju_copy(d->qpos, p, m->nq); p += m->nq;
+  mju_copy(d->qvel, p, m->nv); p += m->nv;
+  mju_copy(d->qacc_warmstart, p, m->nv); p += m->nv;
+  mju_copy(d->ctrl, p, m->nu);
+}
+
+int any_model(mjModel* m, const char* mode, const char* path, bool device_cost) {
+  if (!read_cases(path, m)) {
+    fprintf(stderr, "FAIL: could not read the cases of %s\n", path);
+    return 1;
+  }
+  stepCostFn_t fn = descCost;
+  if (device_cost) {
+    ilqg_cost c{};
+    const Cases& C = g_cases;
+    c.wq = C.a[0].data(); c.tq = C.a[1].data(); c.lq = C.a[2].data();
+    c.wv = C.a[3].data(); c.tv = C.a[4].data(); c.lv = C.a[5].data();
+    c.wu = C.a[6].data(); c.tu = C.a[7].data(); c.lu = C.a[8].data();
+    ilqg_legacy::register_cost(fn, &c, m->nq, m->nv, m->nu);
+  }
+  const int nv = m->nv, nu = m->nu, D = nv * (2 * nv + nu) + 2 * nv + nu;
+  std::vector<mjtNum> deriv((size_t)D, 0.0);
+  mjData* d = mj_makeData(m);
+  for (const auto& s : g_cases.states) {
+    load_state(m, d, s);
+    if (!strcmp(mode, "costcols")) {
+      ilqg_legacy::host_cost_columns(m, d, fn, deriv.data());
+      hex("g", deriv.data() + nv * (2 * nv + nu), 2 * nv + nu);
+    } else {
+      calcMJDerivatives(m, d, deriv.data(), fn);
+      hex("deriv", deriv.data(), D);
+    }
+  }
+  mj_deleteData(d);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, const char** argv) {
   if (argc < 3) {
-    fprintf(stderr, "usage: legacy_members model.xml members | initv [iters] | mu value [iters] | mutate\n");
+    fprintf(stderr, "usage: legacy_members model.xml members | initv [iters] | mu value [iters] | mutate |\n"
+                    "       costcols cases.txt | fd cases.txt [--device-cost];  legacy_members - quat seed count\n");
     return 2;
   }
+  if (!strcmp(argv[2], "quat"))
+    return quat_cases(argc > 3 ? strtoull(argv[3], nullptr, 10) : 1, argc > 4 ? atoi(argv[4]) : 3000);
   mj_activate("mjkey.txt");
   char error[1000] = "";
   mjModel* m = mj_loadXML(argv[1], 0, error, 1000);
   if (!m) mju_error_s("Load model error: %s", error);
+  if (!strcmp(argv[2], "costcols") || !strcmp(argv[2], "fd")) {
+    if (argc < 4) mju_error("legacy_members: the cases file is missing");
+    const int rc = any_model(m, argv[2], argv[3], argc > 4 && !strcmp(argv[4], "--device-cost"));
+    mj_deleteModel(m);
+    return rc;
+  }
   if (m->nv != kNv || m->nu != kNu) mju_error("legacy_members drives the inverted pendulum (nv=2, nu=1)");
   mjData* d = mj_makeData(m);
   for (int i = 0; i < 10; i++) mj_step(m, d);  // inverted_pendulum.cpp:12-13

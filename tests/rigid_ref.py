@@ -7,12 +7,16 @@ composite-rigid-body pass, no recursive Newton-Euler, no sparse LDL.
   kinematics   product of exponentials in the world frame: a body's pose at q is
                its qpos0 pose moved by the screw of each ancestor dof, root to leaf
   Jacobians    world frame, column by column; the free joint follows MuJoCo's
-               convention (linear velocity in the world frame, angular in the body frame)
+               convention (linear velocity in the world frame, angular in the body frame);
+               a ball joint is three rotational dofs about the axes of its body's frame,
+               anchored at the joint's world position, all carried by the ancestors' dofs
+               and by the ball's own rotation
   M(q)         sum_b m_b Jp_b'Jp_b + Jr_b' I_b(q) Jr_b + diag(armature)
   c(q, v)      sum_b m_b Jp_b'(Jp_b_dot v - g) + Jr_b'(I_b Jr_b_dot v + w_b x I_b w_b)
   qacc_smooth  M^-1 tau by Gaussian elimination with partial pivoting
   integrators  Euler with MuJoCo's implicit damping, RK4 stage by stage (valid
-               only while no constraint is active; asserted)
+               only while no constraint is active; asserted); free and ball quaternions
+               advance by the exponential of the body-frame angular velocity
   collisions   plane/sphere/capsule pairs; capsule-capsule by enumeration
   constraints  limit and contact rows, D, aref; the convex cost and its exact
                minimiser by an active-set Newton iteration
@@ -21,7 +25,8 @@ Every function works in the dtype the Ref was made with, so the same formulas
 run in float64 measure the reference's own rounding (E64 in the tests).
 
 MuJoCo conventions that are not physics are restated here and marked
-"convention": the contact point at half the penetration, the tangent frame of a
+"convention": a ball joint carries damping and armature but neither a spring
+nor a limit (the product refuses both), the contact point at half the penetration, the tangent frame of a
 contact, two contacts for exactly parallel capsules, the order of rows.
 """
 import numpy as np
@@ -113,12 +118,15 @@ class Ref:
         self.jq, self.jd, self.bjoints = [], [], [[] for _ in range(self.nb)]
         aq = ad = 0
         for ji, j in enumerate(C.joints):
-            assert j["type"] in ("free", "hinge", "slide"), "ball joints are not in the supported models"
+            assert j["type"] in ("free", "ball", "hinge", "slide")
+            if j["type"] == "ball":   # convention: the product simulates neither, and refuses both
+                assert not j["limited"] and j["stiffness"] == 0, "a ball joint with a limit or a spring"
             self.jq.append(aq)
             self.jd.append(ad)
             self.bjoints[j["body"]].append(ji)
-            aq += 7 if j["type"] == "free" else 1
-            ad += 6 if j["type"] == "free" else 1
+            aq += {"free": 7, "ball": 4}.get(j["type"], 1)
+            ad += {"free": 6, "ball": 3}.get(j["type"], 1)
+        self.R0 = T([mi.qmat(b["gquat"]) for b in C.bodies])   # body frames at qpos0, world
         self.chain = [[] for _ in range(self.nb)]   # dofs that move body b, root to leaf
         self.carr = [None] * self.nv                # dofs that move the axis / anchor of dof i
         self.rot = [False] * self.nv
@@ -133,6 +141,13 @@ class Ref:
                         self.carr[d0 + k] = ch + list(range(d0, d0 + 6))
                         self.rot[d0 + k] = True
                     ch += list(range(d0, d0 + 6))
+                elif C.joints[ji]["type"] == "ball":
+                    # the body's frame after the joint's rotation: no later joint may turn it again
+                    assert ji == self.bjoints[b][-1], "a ball joint must be the last joint of its body"
+                    ch += list(range(d0, d0 + 3))
+                    for k in range(3):       # body axes: carried by the ancestors and the ball itself
+                        self.carr[d0 + k] = list(ch)
+                        self.rot[d0 + k] = True
                 else:
                     ch.append(d0)
                     self.carr[d0] = list(ch)
@@ -170,6 +185,16 @@ class Ref:
                         an[da + k] = q[qa:qa + 3].copy()
                         ax[da + 3 + k] = Rq[:, k].copy()
                         an[da + 3 + k] = q[qa:qa + 3].copy()
+                    continue
+                if j["type"] == "ball":    # T <- T o E0, E0 the body-frame rotation about r0, seen at qpos0
+                    r0, R0 = self.T(j["gpos"]), self.R0[b]
+                    quat = q[qa:qa + 4] / np.sqrt(q[qa:qa + 4] @ q[qa:qa + 4])
+                    E = R0 @ mi.qmat(quat).astype(dt) @ R0.T
+                    anchor = Rb @ r0 + pb
+                    pb = Rb @ (r0 - E @ r0) + pb
+                    Rb = Rb @ E
+                    for k in range(3):
+                        ax[da + k], an[da + k] = (Rb @ R0)[:, k].copy(), anchor.copy()
                     continue
                 a0, r0 = self.T(j["gaxis"]), self.T(j["gpos"])
                 a0 = a0 / np.sqrt(a0 @ a0)
@@ -252,7 +277,7 @@ class Ref:
         q, v = self.T(q), self.T(v)
         f = -self.damping * v
         for ji, j in enumerate(self.C.joints):
-            if j["type"] == "free" or j["stiffness"] == 0:
+            if j["type"] in ("free", "ball") or j["stiffness"] == 0:
                 continue
             spring = self.dt(j["springref"] * (self.C.angle_unit if j["type"] == "hinge" else 1.0))
             f[self.jd[ji]] -= self.dt(j["stiffness"]) * (q[self.jq[ji]] - spring)
@@ -295,21 +320,23 @@ class Ref:
 
     # ---------------------------------------------------------------- integration
     def integrate_pos(self, q, v, h):
-        """q (+) h v; a free joint's quaternion by the exponential of the body-frame angular velocity"""
+        """q (+) h v; a free or ball joint's quaternion by the exponential of the body-frame angular velocity"""
         q, v = self.T(q).copy(), self.T(v)
         for ji, j in enumerate(self.C.joints):
             qa, da = self.jq[ji], self.jd[ji]
-            if j["type"] != "free":
+            if j["type"] not in ("free", "ball"):
                 q[qa] += h * v[da]
                 continue
-            q[qa:qa + 3] += h * v[da:da + 3]
-            w = v[da + 3:da + 6]
+            if j["type"] == "free":
+                q[qa:qa + 3] += h * v[da:da + 3]
+                qa, da = qa + 3, da + 3
+            w = v[da:da + 3]
             n = np.sqrt(w @ w)
-            quat = q[qa + 3:qa + 7] / np.sqrt(q[qa + 3:qa + 7] @ q[qa + 3:qa + 7])
+            quat = q[qa:qa + 4] / np.sqrt(q[qa:qa + 4] @ q[qa:qa + 4])
             if n > 0:
                 ang = h * n
                 quat = mi.qmul(quat, np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * w / n]).astype(self.dt))
-            q[qa + 3:qa + 7] = quat
+            q[qa:qa + 4] = quat
         return q
 
     def _free_qacc(self, q, v, ctrl, qf, xf):
@@ -430,7 +457,7 @@ class Ref:
         convention: the lower side first"""
         q, rows = self.T(q), []
         for ji, j in enumerate(self.C.joints):
-            if not j["limited"] or j["type"] == "free":
+            if not j["limited"] or j["type"] in ("free", "ball"):
                 continue
             for side, dist in ((+1, q[self.jq[ji]] - self.dt(j["range"][0])), (-1, self.dt(j["range"][1]) - q[self.jq[ji]])):
                 if dist < self.dt(j["margin"]):
@@ -444,7 +471,7 @@ class Ref:
         """smallest distance of a limited joint to either end of its range"""
         q, out = self.T(q), None
         for ji, j in enumerate(self.C.joints):
-            if j["limited"] and j["type"] != "free":
+            if j["limited"] and j["type"] not in ("free", "ball"):
                 d = min(q[self.jq[ji]] - self.dt(j["range"][0]), self.dt(j["range"][1]) - q[self.jq[ji]])
                 out = d if out is None else min(out, d)
         return out

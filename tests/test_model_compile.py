@@ -154,3 +154,38 @@ def test_model_lds_limit_refused_at_load(ia):
     assert (small.nv, small.nu) == (4, 4)
     with pytest.raises(ia.IlqgError, match=r"code 4\).*exceeds one CU's LDS"):
         ia.Model.from_string(_chain_xml(48))
+
+
+def test_limited_ball_joint_refused(ia):
+    """limit rows are built for slide and hinge joints only, so a ball joint with
+    limited="true" would be simulated without its limit.  Like stiffness on a ball or
+    free joint it is refused where the device would first run the model (forward / step /
+    FD batches and the solver's creation; the check precedes every device call, so it
+    needs no GPU): ILQG_ERR_UNSUPPORTED with a message naming the joint.  The same
+    model with limited="false" (range kept) loads and passes the check"""
+    from ball_models import BALLARM_XML
+    shoulder, wrist = '<joint name="shoulder" type="ball" ', '<joint name="wrist" type="ball" '
+    assert BALLARM_XML.count(shoulder) == 1 and BALLARM_XML.count(wrist) == 1
+
+    def first_use(xml):
+        m = ia.Model.from_string(xml)
+        assert (m.nq, m.nv) == (10, 8)
+        st = m.reset_state(1)
+        return m, [lambda: m.forward(st), lambda: m.step(st, 1), lambda: m.calc_derivatives(st),
+                   lambda: ia.ILQR(m, st, 5, ia.Cost(wv=[1.0] * 8))]
+
+    for tag, j in ((shoulder, 0), (wrist, 2)):
+        for use in first_use(BALLARM_XML.replace(tag, tag + 'limited="true" range="0 0.5" '))[1]:
+            with pytest.raises(ia.IlqgError, match=rf"code 4\).*limited ball joint \(joint {j}\)"):
+                use()
+    for use in first_use(BALLARM_XML.replace(shoulder, shoulder + 'stiffness="2" '))[1]:
+        with pytest.raises(ia.IlqgError, match=r"code 4\).*stiffness on ball/free joints"):
+            use()
+    m, uses = first_use(BALLARM_XML.replace(shoulder, shoulder + 'limited="false" range="0 0.5" '))
+    assert _fields(m.blob())["jnt_range"].reshape(-1, 2)[0].tolist() == [0.0, 0.5]
+    assert _fields(m.blob())["jnt_limited"].tolist() == [0, 1, 0, 0]
+    for use in uses:  # with a GPU it runs; without one the failure is the missing device, not a refusal
+        try:
+            use()
+        except ia.IlqgError as e:
+            assert "code 4)" not in str(e) and "ball" not in str(e), str(e)

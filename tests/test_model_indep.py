@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 import mjcf_indep as mi
+from ball_models import BALL_XML, ball_file, ball_model
 from conftest import model_path
 from test_model_compile import _fields
 
-MODELS = ["inverted_pendulum", "hopper", "humanoid"]
+MODELS = ["inverted_pendulum", "hopper", "humanoid", "ballarm", "floatarm"]
 RTOL, ATOL = 1e-10, 1e-12
 
 
@@ -40,16 +41,37 @@ def world_frames(f, qpos0):
         xpos[b] = xpos[p] + qmat(xq[p]) @ bp[b]
         xq[b] = mi.qmul(xq[p], bq[b])
         for j in range(f["body_jntadr"][b], f["body_jntadr"][b] + f["body_jntnum"][b]):
+            a = f["jnt_qposadr"][j]
             if f["jnt_type"][j] == 0:
-                a = f["jnt_qposadr"][j]
                 xpos[b], xq[b] = qpos0[a:a + 3], qpos0[a + 3:a + 7]
+            elif f["jnt_type"][j] == 1:  # ball: the body turns by its quaternion about the joint's anchor
+                anchor = xpos[b] + qmat(xq[b]) @ f["jnt_pos"].reshape(-1, 3)[j]
+                xq[b] = mi.qmul(xq[b], qpos0[a:a + 4])
+                xpos[b] = anchor - qmat(xq[b]) @ f["jnt_pos"].reshape(-1, 3)[j]
     return xpos, xq
 
 
 @pytest.fixture(scope="module", params=MODELS)
 def pair(request, ia):
+    if request.param in BALL_XML:  # written in the tests: ball joints, the generic kernels
+        m = ball_model(ia, request.param)
+        return request.param, _fields(m.blob()), m, mi.compile_mjcf(ball_file(request.param))
     m = ia.Model.load(model_path(request.param))
     return request.param, _fields(m.blob()), m, mi.compile_mjcf(model_path(request.param))
+
+
+def test_ball_models_have_ball_joints(pair):
+    """the two written models carry what they are here for: ballarm a ball joint as the
+    tree's first joint and one below a hinge, floatarm a ball joint below a free joint"""
+    name, f, m, r = pair
+    types = [j["type"] for j in r.joints]
+    if name == "ballarm":
+        assert types == ["ball", "hinge", "ball", "hinge"] and list(f["jnt_type"]) == [1, 3, 1, 3]
+        assert all(np.any(np.abs(j["pos"]) > 0) for j in r.joints if j["type"] == "ball")
+    elif name == "floatarm":
+        assert types == ["free", "ball", "hinge"] and list(f["jnt_type"]) == [0, 1, 3]
+    else:
+        assert "ball" not in types
 
 
 def test_sizes_topology_options(pair):

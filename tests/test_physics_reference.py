@@ -18,20 +18,34 @@ import pytest
 
 import mjcf_indep as mi
 import rigid_ref as rr
+from ball_models import BALL_XML, ball_file, ball_model
 from conftest import model_path
 from test_riccati_cases import chain_xml
 
 LD = np.longdouble
-MODELS = ["inverted_pendulum", "hopper", "humanoid", "chain"]
+MODELS = ["inverted_pendulum", "hopper", "humanoid", "chain", "ballarm", "floatarm"]
 NSTATE = 8
 
 
 def compiled(name):
+    if name in BALL_XML:
+        return mi.compile_mjcf(ball_file(name))
     return mi.compile_mjcf(io.StringIO(chain_xml())) if name == "chain" else mi.compile_mjcf(model_path(name))
 
 
 def product_model(ia, name):
+    if name in BALL_XML:
+        return ball_model(ia, name)
     return ia.Model.from_string(chain_xml()) if name == "chain" else ia.Model.load(model_path(name))
+
+
+def _far_quat(rng):
+    """a unit quaternion far from the identity, every component away from 0"""
+    axis = rng.uniform(0.3, 1.0, 3) * rng.choice([-1.0, 1.0], 3)
+    axis /= np.linalg.norm(axis)
+    ang = rng.uniform(0.6, 2.6)
+    quat = np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * axis])
+    return quat / np.linalg.norm(quat)
 
 
 def rel(a, b):
@@ -57,6 +71,11 @@ def _candidate(name, C, rng, k):
             v[ad:ad + 3] = rng.normal(0, 1.0, 3)
             v[ad + 3:ad + 6] = rng.normal(0, 4.0, 3)
             aq, ad = aq + 7, ad + 6
+            continue
+        if j["type"] == "ball":
+            q[aq:aq + 4] = _far_quat(rng)
+            v[ad:ad + 3] = rng.normal(0, 3.0, 3)
+            aq, ad = aq + 4, ad + 3
             continue
         if j["limited"]:
             lo, hi = j["range"]
@@ -133,7 +152,11 @@ class Batch:
                 quat = s["q"][aq + 3:aq + 7]
                 assert abs(np.linalg.norm(quat) - 1) <= 2.3e-16
                 assert 2 * np.arccos(abs(quat[0])) >= 0.5 and np.all(np.abs(quat[1:]) > 0.05)
-            aq += 7 if j["type"] == "free" else 1
+            if j["type"] == "ball":
+                quat = s["q"][aq:aq + 4]
+                assert abs(np.linalg.norm(quat) - 1) <= 2.3e-16
+                assert 2 * np.arccos(abs(quat[0])) >= 0.5 and np.all(np.abs(quat[1:]) > 0.05)
+            aq += {"free": 7, "ball": 4}.get(j["type"], 1)
 
     @staticmethod
     def _run(R, s):
@@ -177,7 +200,8 @@ def test_jacobian_rate_against_richardson(name):
     the velocity (nine chained hinges at 3 rad/s each reach 3e-10), so the batch's
     velocities are scaled by a quarter here; the closed form is exact at any speed.
     Measured: pendulum 1.7e-15, hopper 2.1e-13, humanoid 2.1e-13, chain 1.1e-12
-    (3e-10 for the chain at full speed, all of it the extrapolation's)."""
+    (3e-10 for the chain at full speed, all of it the extrapolation's), ballarm 2.5e-13,
+    floatarm 1.8e-13 (ball joints: the rate of the body axes under the ball's own rotation)."""
     B = batch(name)
     R = B.R
     worst = 0.0
@@ -298,6 +322,8 @@ def test_oracle_smooth_dynamics(ia, ora, name, key):
       hopper             1.7e-16/2.7e-16  3.9e-16/4.0e-16  3.1e-15/1.4e-15  1.6e-15/1.7e-15
       humanoid           2.9e-16/5.7e-16  5.1e-16/5.6e-16  2.8e-15/1.9e-15  1.5e-14/2.0e-14
       chain              3.0e-16/1.9e-16  6.4e-16/6.3e-16  1.8e-15/8.1e-16  3.7e-15/5.6e-15
+      ballarm            5.2e-16/4.6e-16  1.5e-15/1.6e-15  1.5e-15/6.6e-15  2.5e-15/3.5e-15
+      floatarm           1.2e-16/2.1e-16  3.2e-16/2.2e-16  2.3e-15/5.0e-15  9.8e-15/1.0e-14
     (no constraint is active, so qacc is qacc_smooth)"""
     B = batch(name)
     om = ora.OModel(product_model(ia, name).blob())
@@ -319,7 +345,9 @@ def test_oracle_steps(ia, ora, name):
       inverted_pendulum  2.5e-16/1.7e-16  8.4e-17/1.4e-16  1.8e-16/1.6e-16  3.5e-16/5.5e-16
       hopper             7.3e-17/7.3e-17  1.2e-16/1.8e-16  1.4e-16/1.5e-16  5.2e-16/4.5e-16
       humanoid           7.8e-17/2.1e-16  1.4e-14/3.7e-14  5.7e-16/8.7e-16  2.9e-15/2.7e-15
-      chain              9.4e-17/9.4e-17  2.3e-16/1.9e-16  2.5e-16/2.5e-16  8.4e-16/1.0e-15"""
+      chain              9.4e-17/9.4e-17  2.3e-16/1.9e-16  2.5e-16/2.5e-16  8.4e-16/1.0e-15
+      ballarm            3.4e-16/3.4e-16  1.4e-16/2.8e-16  5.3e-16/6.5e-16  1.1e-15/6.1e-16
+      floatarm           6.3e-17/6.3e-17  2.6e-16/3.9e-16  1.5e-16/1.5e-16  1.1e-15/2.5e-15"""
     B = batch(name)
     om = ora.OModel(product_model(ia, name).blob())
     devs = dict(q1=0.0, v1=0.0, q10=0.0, v10=0.0)
@@ -470,6 +498,17 @@ CONTACT_CASES = {
         ("rest pose", [0.0, 0.0, 0.0]),
         ("shifted along the axis", [0.003, -0.2, 0.0]),
     ],
+    "ballarm": [
+        ("the hand sphere on the floor",
+         [0.9474701826353175, -0.036599007054861875, 0.31103605995562766, -0.06494101251809571, 0.697937,
+          0.7901337836246584, 0.41084788749075934, 0.3936028922132403, -0.2279679375717867, -0.07322]),
+        ("the finger capsule flat on the floor: two contacts",
+         [0.755206759905838, 0.48578584555971727, 0.1976859371519934, -0.3931858749989563, -0.542051,
+          0.8951127601317426, -0.16334595622729153, 0.36204490298084907, 0.20252094572935556, 1.348883]),
+        ("the hand sphere and both ends of the finger capsule on the floor, the arm moving",
+         [-0.6810432623263374, 0.4687011805357616, -0.5625602166886736, 0.005028001936701243, -0.103403,
+          0.6302000459586005, -0.436061031800624, -0.15752001148746228, -0.6228050454193053, -0.921498]),
+    ],
 }
 CONTACT_MODELS = list(CONTACT_CASES)
 REQUIRED_KINDS = ["plane-sphere", "plane-capsule one contact", "plane-capsule two contacts", "sphere-capsule end",
@@ -541,6 +580,20 @@ class ContactBatch:
                 assert s["nlimit"] == 0 and R.limit_clearance(s["q"]) > 0
                 assert all(C.geoms[c["g1"]]["type"] != "plane" for c in s["P"].contacts)
             assert {"sphere-capsule end", "sphere-capsule interior", "capsule-capsule edge"} <= self.kinds
+        if self.name == "ballarm":
+            pairs = [sorted((C.geoms[c["g2"]]["type"], c["kind"]) for c in s["P"].contacts) for s in S]
+            assert pairs[0] == [("sphere", "plane-sphere")]
+            assert pairs[1] == [("capsule", "plane-capsule")] * 2 and len({c["g2"] for c in S[1]["P"].contacts}) == 1
+            assert pairs[2] == [("capsule", "plane-capsule")] * 2 + [("sphere", "plane-sphere")]
+            assert all(C.geoms[c["g1"]]["type"] == "plane" for s in S for c in s["P"].contacts)
+            for s in S:  # inside the elbow's range, both ball quaternions at least 0.5 rad from the identity
+                assert s["nlimit"] == 0 and R.limit_clearance(s["q"]) > 0
+                for a in (0, 5):
+                    assert abs(np.linalg.norm(s["q"][a:a + 4]) - 1) <= 2.3e-16
+                    assert 2 * np.arccos(abs(s["q"][a])) >= 0.5
+            for c in S[2]["P"].contacts:  # moving: the speed of the arm's point at each contact
+                vel = R.jac(S[2]["P"].f.K, C.geoms[c["g2"]]["body"], c["pos"])[0] @ S[2]["P"].f.v
+                assert np.sqrt(vel @ vel) >= 0.1
         if self.name in TEST_XML:
             for s in S:
                 K = s["P"].f.K
@@ -615,6 +668,7 @@ def test_oracle_contacts_and_rows(ia, ora, name):
       humanoid   8.5e-14/8.4e-14  3.4e-15/8.3e-15  1.4e-16/2.6e-16  5.8e-15/8.6e-15  2.2e-16/2.1e-15  9.5e-14/9.9e-14
       cross      1.3e-14/3.5e-14  1.2e-15/2.0e-15  1.6e-16/2.1e-16  1.2e-15/2.0e-15  2.9e-16/2.9e-16  4.3e-15/9.2e-15
       parallel   3.3e-16/3.3e-16  0 / 0            2.8e-18/2.8e-18  0 / 0            9.6e-17/3.5e-16  8.2e-17/2.0e-16
+      ballarm    2.5e-14/3.2e-14  0 / 0            8.1e-16/8.1e-16  5.6e-16/7.1e-16  8.9e-17/7.4e-16  1.1e-14/9.7e-15
     efc_pos follows dist."""
     B = cbatch(name)
     om = ora.OModel(contact_product(ia, name).blob())
@@ -649,7 +703,8 @@ def test_oracle_constraint_solve(ia, ora, name):
     Newton step the remaining gap is no larger than that improvement, 10x allows for it.
     Measured on the CPU: the gap is between -4.1e-16 and 1.2e-16 in every case (zero at the
     rounding of the two costs in longdouble), |qacc - a*|_M at most 1.1e-11 (humanoid, head
-    against a hand), one to four iterations, never the cap."""
+    against a hand), one to four iterations, never the cap (ballarm: gap within -2.1e-16 ..
+    4.2e-16, |qacc - a*|_M at most 1.0e-12, two to four iterations)."""
     B = cbatch(name)
     om = ora.OModel(contact_product(ia, name).blob())
     worst = 0.0
