@@ -369,7 +369,9 @@ struct ilqg_solver {
   // trajectory point, [P][csz], shared by every seed; sched[sched_cur] is the
   // table in force and the other buffer the target of the next shift (a shift
   // in place would overlap itself).  host_cost: the creation cost, packed.
-  bool sched_on = false;
+  // sched_seeds (ilqg_solver_set_cost_schedule_seeds): the buffers hold one such
+  // table per seed, [S][P][csz], and sstride() is the doubles from one to the next.
+  bool sched_on = false, sched_seeds = false;
   int sched_cur = 0, csz = 0;
   DevBuf sched[2];
   std::vector<double> host_cost;
@@ -412,12 +414,18 @@ struct ilqg_solver {
   CostDev cview0() const { return cat(cost.as<double>()); }
   // the cost the launches charge: the creation cost, or row p0 of the schedule
   // (a launch whose point 0 is the trajectory's point p0) with cstride() doubles
-  // from one point's row to the next (0 without a schedule)
-  CostDev cview(int p0 = 0) const {
+  // from one point's row to the next (0 without a schedule).  s0: the launch's
+  // first seed -- its kernels count seeds from 0, so with a per-seed schedule
+  // the view starts at seed s0's table and seed s0 + i's is i sstride() doubles
+  // further on (0 unless per seed), the global seed's in every launch.
+  CostDev cview(int p0 = 0, int s0 = 0) const {
     if (!sched_on) return cview0();
-    return cat(sched[sched_cur].as<double>() + (size_t)p0 * csz);
+    return cat(sched[sched_cur].as<double>() + (size_t)s0 * sstride() + (size_t)p0 * csz);
   }
   int cstride() const { return sched_on ? csz : 0; }
+  int sstride() const { return sched_on && sched_seeds ? P * csz : 0; }
+  // tables in the schedule's buffers
+  size_t sched_tables() const { return sched_seeds ? (size_t)S : 1; }
   CostDev cat(const double* c) const {
     const int nq = model->host.nq, nv = model->host.nv, nu = model->host.nu;
     return CostDev{c, c + nq, c + 2 * nq, c + 3 * nq, c + 3 * nq + nv, c + 3 * nq + 2 * nv,
@@ -752,7 +760,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     a.Dp = Dp; a.WCp = WCp; a.qfrc_applied = s.qa.as<double>(); a.xfrc_applied = s.xf.as<double>(); a.cost = cd;
     a.cw = cw.as<double>(); a.deriv = outp.as<double>(); a.sync = sy.as<unsigned>(); a.fault = fl.as<unsigned>();
     a.nt_replay = nt_replay;
-    HIPCHK(launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, m->stream, 0));
+    HIPCHK(launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, m->stream, 0, 0));
     HIPCHK(hipStreamSynchronize(m->stream));
     unsigned flt = 0;
     HIPCHK(hipMemcpy(&flt, fl.p, 4, hipMemcpyDeviceToHost));
@@ -760,7 +768,7 @@ int ilqg_fd_batch(const ilqg_model* mc, int n, const double* qpos, const double*
     HIPCHK(hipMemcpy2D(deriv, (size_t)D * 8, outp.p, (size_t)Dp * 8, (size_t)D * 8, n, hipMemcpyDeviceToHost));
     return ILQG_OK;
   } else {
-    const FdArgs fa{st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd, 0, s.warm_c.as<double>(),
+    const FdArgs fa{st, n, 1, s.qa.as<double>(), s.xf.as<double>(), cd, 0, 0, s.warm_c.as<double>(),
                     s.cost_c.as<double>(), s.out.as<double>(), D, m->stream, nt_replay};
     HIPCHK(launch_fd_centre_coop(m->dm, m->Lc, m->C, m->X, fa));
     HIPCHK(launch_fd_cols_coop(m->dm, m->Lc, m->C, m->X, fa));
@@ -1044,8 +1052,8 @@ static RollArgs roll_args(ilqg_solver* s, const SeedRange& r, RollChunk ch) {
   return RollArgs{r.ns, s->A, s->P, nom, multi ? toff(s->tview(s->cand), s0 * A * P, h) : nom, multi ? 1 : 0,
                   s->K.as<double>() + s0 * P * h.nu * nx, s->k.as<double>() + s0 * P * h.nu, s->alphas.as<double>(),
                   toff(s->tview(s->dinit), s0, h), s->qfrc_applied.as<double>() + s0 * h.nv,
-                  s->xfrc_applied.as<double>() + s0 * 6 * h.nbody, 0, s->cview(), s->cost_cand.as<double>() + s0 * A,
-                  r.st, ch, s->cstride()};
+                  s->xfrc_applied.as<double>() + s0 * 6 * h.nbody, 0, s->cview(0, r.s0), s->cost_cand.as<double>() + s0 * A,
+                  r.st, ch, s->cstride(), s->sstride()};
 }
 static hipError_t forward_range(ilqg_solver* s, const SeedRange& r, hipEvent_t before_select = nullptr) {
   const ilqg_model* m = s->model;
@@ -1291,7 +1299,7 @@ static hipError_t fused_launch(ilqg_solver* s, const SeedRange& r, int mode, boo
   a.WCp = s->WCp;
   a.qfrc_applied = s->qfrc_applied.as<double>() + s0 * h.nv;
   a.xfrc_applied = s->xfrc_applied.as<double>() + s0 * 6 * h.nbody;
-  a.cost = s->cview();
+  a.cost = s->cview(0, r.s0);
   a.cw = s->cw.as<double>() + s0 * P * s->WCp;
   a.deriv = s->deriv.as<double>() + s0 * P * s->Dp;
   a.sync = r.sync;
@@ -1355,7 +1363,7 @@ static hipError_t fused_launch(ilqg_solver* s, const SeedRange& r, int mode, boo
     if (e != hipSuccess) return e;
     a.order = s->plan_order.as<unsigned>();
   }
-  return launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, r.st, s->cstride());
+  return launch_fd_fused_coop(m->dm, m->Lc, m->C, m->X, a, r.st, s->cstride(), s->sstride());
 }
 
 // the two-kernel FD sweep (fp64 or fp32) of npts points from point p0 of seed
@@ -1364,7 +1372,7 @@ static FdArgs fd_args(ilqg_solver* s, int sd, int p0, int npts, int P, hipStream
   const HostModel& h = s->model->host;
   const size_t pt0 = (size_t)sd * s->P + p0;
   return FdArgs{toff(s->tview(s->traj), pt0, h), npts, P, s->qfrc_applied.as<double>() + (size_t)sd * h.nv,
-                s->xfrc_applied.as<double>() + (size_t)sd * 6 * h.nbody, s->cview(p0), s->cstride(),
+                s->xfrc_applied.as<double>() + (size_t)sd * 6 * h.nbody, s->cview(p0, sd), s->cstride(), s->sstride(),
                 s->warm_c.as<double>() + pt0 * h.nv, s->cost_c.as<double>() + pt0,
                 s->deriv.as<double>() + pt0 * s->Dp, s->Dp, st, s->nt_replay};
 }
@@ -1403,7 +1411,8 @@ static hipError_t fd_points_launch(ilqg_solver* s, const FdArgs& a) {
 // the same records the whole-trajectory sweep writes.
 static hipError_t fd_range_launch(ilqg_solver* s, int p0, int np, hipStream_t st) {
   // the kernels' seed index pt / P is 0 for every point of the range, and their
-  // point index pt % P counts from p0: the cost schedule is passed from row p0 on
+  // point index pt % P counts from p0: the cost schedule is passed from row p0
+  // of seed sd's table on
   constexpr int kOneSeed = 1 << 30;
   for (int sd = 0; sd < s->S; sd++) {
     const hipError_t e = fd_points_launch(s, fd_args(s, sd, p0, np, kOneSeed, st));
@@ -1433,7 +1442,8 @@ int ilqg_fd_sweep_range(ilqg_solver* s, int p0, int np) {
 //  - the FD records of the compact trajectory through fd_points_launch, the
 //    launch fd_range_launch makes per seed -- here once for every seed, P =
 //    n + 1 points per seed, so seed pt / P carries its forces and point pt % P
-//    its cost row.  (Measured: fd_range_launch(s, 0, n) itself, S launch pairs
+//    its cost row, of seed pt / P's table when the schedule is per seed (the
+//    seed stride is the resident table's, not the launch's P).  (Measured: fd_range_launch(s, 0, n) itself, S launch pairs
 //    of one FD evaluation's latency each, took 1.4 ms of a 1.5 ms tick on the
 //    bench workload, dealt over four streams still 1.1 ms: DESIGN.md.)  Point
 //    n's record is computed once more and dropped;
@@ -1492,7 +1502,7 @@ int ilqg_solver_shift_horizon(ilqg_solver* s, int n, int tail) {
   }));
   HIPCHK(s->timed(3, [&] {
     return fd_points_launch(s, FdArgs{tl, s->S * (n + 1), n + 1, s->qfrc_applied.as<double>(),
-                                      s->xfrc_applied.as<double>(), s->cview(0), s->cstride(),
+                                      s->xfrc_applied.as<double>(), s->cview(0), s->cstride(), s->sstride(),
                                       s->warm_c.as<double>(), s->cost_c.as<double>(), s->shift_rec.as<double>(),
                                       s->Dp, s->stream, s->nt_replay});
   }));
@@ -1522,12 +1532,12 @@ int ilqg_backward(ilqg_solver* s) {
     if (s->reg_on)
       return launch_backward_std_reg(m->dm, s->S, s->P, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
                                      s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
-                                     s->flags(), StdDev{s->cview(), s->cstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
+                                     s->flags(), StdDev{s->cview(), s->cstride(), s->sstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
                                      s->rview(s->reg_iter - 1), s->stream);
     if (s->recursion == ILQG_RECURSION_STANDARD)
       return launch_backward_std(m->dm, s->S, s->P, s->opts.mu, s->deriv.as<double>(), s->Dp, s->tview(s->traj),
                                  s->K.as<double>(), s->k.as<double>(), s->V.as<double>(), s->v.as<double>(),
-                                 s->flags(), StdDev{s->cview(), s->cstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
+                                 s->flags(), StdDev{s->cview(), s->cstride(), s->sstride(), s->ex_dV.as<double>(), s->ex_bad.as<int>()},
                                  s->stream);
     // control limits: the boxed recursion (set_ctrl_limits keeps the MFMA engine out)
     if (s->limits)
@@ -1882,27 +1892,41 @@ static bool all_finite(const double* a, size_t n) {
   return true;
 }
 
-int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows) {
-  if (!s) return fail(ILQG_ERR_ARG, "null solver");
-  const size_t n = (size_t)s->P * s->csz;
+// the shared table ([P][csz]) or one table per seed ([S][P][csz]) into the
+// buffer in force; either replaces the other
+static int sched_set(ilqg_solver* s, const double* rows, bool seeds) {
   if (!rows) {  // off: the solver as it was created
     HIPCHK(s->sync_all());
-    s->sched_on = false;
+    s->sched_on = s->sched_seeds = false;
     return reg_invalidate(s);
   }
+  const size_t n = (seeds ? (size_t)s->S : 1) * s->P * s->csz;
   if (!all_finite(rows, n)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
   HIPCHK(s->sync_all());  // launches already enqueued keep the rows they were given
   for (auto& b : s->sched)
-    if (!b.p) HIPCHK(b.alloc(n * 8));
+    if (b.n != n * 8) HIPCHK(b.alloc(n * 8));
   HIPCHK(hipMemcpy(s->sched[s->sched_cur].p, rows, n * 8, hipMemcpyHostToDevice));
   s->sched_on = true;
+  s->sched_seeds = seeds;
   return reg_invalidate(s);
+}
+
+int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  return sched_set(s, rows, false);
+}
+
+int ilqg_solver_set_cost_schedule_seeds(ilqg_solver* s, const double* rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  return sched_set(s, rows, true);
 }
 
 int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled) {
   if (!s) return fail(ILQG_ERR_ARG, "null solver");
   if (enabled) *enabled = s->sched_on ? 1 : 0;
   if (!rows) return ILQG_OK;
+  if (s->sched_seeds)
+    return fail(ILQG_ERR_ARG, "cost schedule: per seed, no single table (ilqg_solver_get_cost_schedule_seeds)");
   if (s->sched_on) {
     HIPCHK(s->sync_all());
     HIPCHK(hipMemcpy(rows, s->sched[s->sched_cur].p, (size_t)s->P * s->csz * 8, hipMemcpyDeviceToHost));
@@ -1912,24 +1936,58 @@ int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled) {
   return ILQG_OK;
 }
 
-int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows) {
+int ilqg_solver_get_cost_schedule_seeds(ilqg_solver* s, double* rows, int* per_seed) {
   if (!s) return fail(ILQG_ERR_ARG, "null solver");
-  if (!s->sched_on) return fail(ILQG_ERR_ARG, "cost schedule: shift without a schedule (set one first)");
+  if (per_seed) *per_seed = s->sched_on && s->sched_seeds ? 1 : 0;
+  if (!rows) return ILQG_OK;
+  const size_t tab = (size_t)s->P * s->csz;
+  if (s->sched_on) {
+    // the tables in force, or the shared one once per seed
+    HIPCHK(s->sync_all());
+    for (int sd = 0; sd < s->S; sd++)
+      HIPCHK(hipMemcpy(rows + sd * tab, s->sched[s->sched_cur].as<double>() + (s->sched_seeds ? sd * tab : 0),
+                       tab * 8, hipMemcpyDeviceToHost));
+  } else {
+    for (size_t p = 0; p < (size_t)s->S * s->P; p++)
+      std::copy(s->host_cost.begin(), s->host_cost.end(), rows + p * s->csz);
+  }
+  return ILQG_OK;
+}
+
+// The receding-horizon tick of every table in force: rows n .. P-1 from rows
+// 0 .. P-1-n, the table's n new rows in front.  new_rows: n rows per table
+// (seeds), or n rows every table takes.
+static int sched_shift(ilqg_solver* s, int n, const double* new_rows, bool seeds) {
   if (n < 1 || n > s->P) return fail(ILQG_ERR_ARG, "cost schedule: shift must be in 1 .. horizon + 1");
   if (!new_rows) return fail(ILQG_ERR_ARG, "cost schedule: null new_rows");
-  const size_t C = s->csz;
-  if (!all_finite(new_rows, (size_t)n * C)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
+  const size_t C = s->csz, nt = s->sched_tables(), tab = (size_t)s->P * C, nn = (size_t)n * C;
+  if (!all_finite(new_rows, (seeds ? nt : 1) * nn)) return fail(ILQG_ERR_ARG, "cost schedule: non-finite entry");
   HIPCHK(s->sync_all());
-  // into the second buffer, then swap: rows n .. P-1 from rows 0 .. P-1-n, the new rows in front
+  // into the second buffer, then swap (a shift in place would overlap itself)
   double* src = s->sched[s->sched_cur].as<double>();
   double* dst = s->sched[1 - s->sched_cur].as<double>();
   // (on the solver's stream and waited for: its streams do not order with the null stream)
-  if (n < s->P)
-    HIPCHK(hipMemcpyAsync(dst + (size_t)n * C, src, (size_t)(s->P - n) * C * 8, hipMemcpyDeviceToDevice, s->stream));
-  HIPCHK(hipMemcpyAsync(dst, new_rows, (size_t)n * C * 8, hipMemcpyHostToDevice, s->stream));
+  for (size_t t = 0; t < nt; t++) {
+    if (n < s->P)
+      HIPCHK(hipMemcpyAsync(dst + t * tab + nn, src + t * tab, (tab - nn) * 8, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(dst + t * tab, new_rows + (seeds ? t * nn : 0), nn * 8, hipMemcpyHostToDevice, s->stream));
+  }
   HIPCHK(hipStreamSynchronize(s->stream));
   s->sched_cur = 1 - s->sched_cur;
   return reg_invalidate(s);
+}
+
+int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (!s->sched_on) return fail(ILQG_ERR_ARG, "cost schedule: shift without a schedule (set one first)");
+  return sched_shift(s, n, new_rows, false);
+}
+
+int ilqg_solver_shift_cost_schedule_seeds(ilqg_solver* s, int n, const double* new_rows) {
+  if (!s) return fail(ILQG_ERR_ARG, "null solver");
+  if (!s->sched_on || !s->sched_seeds)
+    return fail(ILQG_ERR_ARG, "cost schedule: per-seed shift without a per-seed schedule (set one first)");
+  return sched_shift(s, n, new_rows, true);
 }
 
 int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* enabled) {

@@ -183,10 +183,13 @@ __device__ inline void load_state(const auto& m, const auto& L, const Team& T, c
 // A kernel variant that takes one more argument is a template with a trailing
 // parameter pack: empty for the instances that exist without the variant (their
 // argument list, and so their code, is what it was), one type for those with.
-// SCH...: the cost schedule's row stride (kernels.h cost_at), `int`; the
-// bodies' `sched` tag is std::bool_constant<(sizeof...(SCH) > 0)>.
+// SCH...: the cost schedule's row stride and its stride from seed to seed
+// (kernels.h cost_at), `int, int`; the bodies' `sched` tag is
+// std::bool_constant<(sizeof...(SCH) > 0)>.
 __device__ constexpr int sched_stride() { return 0; }
-__device__ constexpr int sched_stride(int cstride) { return cstride; }
+__device__ constexpr int sched_stride(int cstride, int) { return cstride; }
+__device__ constexpr int sched_seed() { return 0; }
+__device__ constexpr int sched_seed(int, int sstride) { return sstride; }
 
 // ---- host side (launch.h: allow_lds, launch, for_model_type) ----
 // The compiled specialisation of a bundled model (static_models.h), if any:

@@ -43,9 +43,20 @@ struct CostDev {
 // and point p is charged with the row `stride` doubles further on per point.
 // The launches below take the stride as `cstride` (0 = one stationary cost:
 // the kernels they always launched); != 0 launches the kernels' scheduled
-// instances (<.., int>), which carry it as an extra last kernel argument.
+// instances (<.., int, int>), which carry it as an extra kernel argument.
+// Per-seed schedule (ilqg_solver_set_cost_schedule_seeds): a second stride,
+// `sstride`, the doubles from one seed's table to the next (0 = one table shared
+// by every seed), the scheduled instances' last argument.  Row (s, p) is
+// cost_at(c, p, cstride) advanced by s * sstride, s the GLOBAL seed: a launch
+// over seeds s0 .. takes the descriptor of seed s0's table, as it takes every
+// other per-seed array from seed s0 on, and its kernels advance by their own
+// seed index.
 __host__ __device__ inline CostDev cost_at(const CostDev& c, int p, int stride) {
   const size_t o = (size_t)p * (size_t)stride;
+  return CostDev{c.wq + o, c.tq + o, c.lq + o, c.wv + o, c.tv + o, c.lv + o, c.wu + o, c.tu + o, c.lu + o};
+}
+__host__ __device__ inline CostDev cost_at(const CostDev& c, int s, int sstride, int p, int stride) {
+  const size_t o = (size_t)s * (size_t)sstride + (size_t)p * (size_t)stride;
   return CostDev{c.wq + o, c.tq + o, c.lq + o, c.wv + o, c.tv + o, c.lv + o, c.wu + o, c.tu + o, c.lu + o};
 }
 
@@ -101,13 +112,14 @@ hipError_t launch_backward_box(const DevModel& m, int S, int P, double mu, const
 size_t backward_box_lds_bytes(int nv, int nu);
 // the standard recursion (ilqg_solver_set_recursion; riccati.h backward_seed
 // with STD): exact diagonal cost Hessians from the cost row of each step's
-// point (cost_at(cost, n, cstride)), mu in Quu / Qux only, no c term.  dV:
+// point (seed s: cost_at(cost, s, sstride, n, cstride)), mu in Quu / Qux only, no c term.  dV:
 // [S][2], the expected reduction's linear and quadratic terms; bad: [S], the
 // first step that took the indefinite-step fallback (K = 0, k = 0), or -1.
 // Models with nq == nv only (the caller checks).
 struct StdDev {
   CostDev cost{};
   int cstride = 0;
+  int sstride = 0;
   double* dV = nullptr;
   int* bad = nullptr;
 };
@@ -262,6 +274,7 @@ struct FdArgs {
   const double *qfrc_applied, *xfrc_applied;
   CostDev cost;
   int cstride;  // cost schedule (cost_at), 0 = none
+  int sstride;  // its stride from seed to seed, 0 = shared
   double *warm_c, *cost_c;
   double* deriv;
   int Ds;
@@ -278,7 +291,8 @@ size_t coop_lds_bytes_f32(const WsLayout& L, const coop::CoopLayout& C);
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, const FdArgs& a, double eps);
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
-                                const coop::CoopAux& X, const FdFused& a, hipStream_t st, int cstride);
+                                const coop::CoopAux& X, const FdFused& a, hipStream_t st, int cstride,
+                                int sstride);
 // a rollout of S seeds x A candidates over a P-point horizon (ch: the points)
 struct RollArgs {
   int S, A, P;
@@ -293,6 +307,7 @@ struct RollArgs {
   hipStream_t st;
   RollChunk ch;
   int cstride;  // cost schedule (cost_at), 0 = none
+  int sstride = 0;  // its stride from seed to seed, 0 = shared
 };
 hipError_t launch_rollout_coop(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, const RollArgs& a);

@@ -12,16 +12,16 @@
 namespace ilqg {
 namespace {
 
-// sched (the kernels' <.., int> instances, launched while a cost schedule is
-// set, kernels.h cost_at; SCH... in coop_common.h): the point's costs are taken
-// from its own row of the schedule, `cstride` doubles per point past the
-// descriptor's arrays
+// sched (the kernels' <.., int, int> instances, launched while a cost schedule
+// is set, kernels.h cost_at; SCH... in coop_common.h): the point's costs are
+// taken from its own row of its seed's schedule, `cstride` doubles per point and
+// `sstride` per seed past the descriptor's arrays
 __device__ inline void fd_centre_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
                                 TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, double* warm_c, double* cost_c,
-                                auto sched, int cstride) {
+                                auto sched, int cstride, int sstride) {
   STAMP_INIT();
   const int pt = blockIdx.x;
-  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt % P, cstride);
+  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt / P, sstride, pt % P, cstride);
   load_state(m, L, T, tr, pt, pt / P, qfrc_applied, xfrc_applied);
   forward_skip(m, L, C, X, T, STAGE_NONE, FD_NITER, 0.0);
   for (int rep = 1; rep < FD_NWARMUP; rep++) forward_skip(m, L, C, X, T, STAGE_VEL, FD_NITER, 0.0);
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_coop(DevMod
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
@@ -52,18 +52,18 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_centre_s(DevModel 
   T.replay = replay;
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_centre_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 __device__ inline void fd_cols_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
                                 TrajDev tr, int P, const double* qfrc_applied, const double* xfrc_applied, CostDev cost, const double* warm_c, const double* cost_c, double* deriv, int Ds,
-                                auto sched, int cstride) {
+                                auto sched, int cstride, int sstride) {
   STAMP_INIT();
   const int nv = m.nv, nu = m.nu;
   const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   const int ncol = nctrl + 2 * nv;
   const int pt = blockIdx.x / ncol, col = blockIdx.x % ncol;
-  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt % P, cstride);
+  if constexpr (decltype(sched)::value) cost = cost_at(cost, pt / P, sstride, pt % P, cstride);
   double* dr = deriv + (size_t)pt * Ds;  // record stride Ds >= D
   const double* wc = warm_c + (size_t)pt * nv;
   const double costCenter = cost_c[pt];
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_coop(DevModel
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // model-specific instance (static_models.h): compile-time sizes, tables and LDS layout
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_cols_s(DevModel mg
   T.replay = replay;
   SM m;
   stage_model_s(mg, L, C, T, m);
-  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_cols_body(m, L, C, X, T, tr, P, qfrc_applied, xfrc_applied, cost, warm_c, cost_c, deriv, Ds, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // ---- fused FD sweep with the backward pass streamed behind it ------------
@@ -273,9 +273,10 @@ __device__ __forceinline__ int snap_dst(int e, const int (&o)[SNAP_NR], const in
   return d;
 }
 
-// (sched, cstride: as fd_centre_body)
+// (sched, cstride, sstride: as fd_centre_body; s is the item's seed, decoded
+// from the ticket's item after the planned order's remap)
 __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                     const FdFused& a, unsigned u, auto sched, int cstride) {
+                                     const FdFused& a, unsigned u, auto sched, int cstride, int sstride) {
   // late tickets first in the SIMD's issue arbitration: they set the launch's tail
   if (u >= a.prio2) __builtin_amdgcn_s_setprio(2);
   else if (u >= a.prio1) __builtin_amdgcn_s_setprio(1);
@@ -308,7 +309,7 @@ __device__ inline void fd_fused_body(const auto& m, const auto& L, const auto& C
   [[maybe_unused]] CostDev prow;
   const CostDev* pc = &a.cost;
   if constexpr (decltype(sched)::value) {
-    prow = cost_at(a.cost, p, cstride);
+    prow = cost_at(a.cost, s, sstride, p, cstride);
     pc = &prow;
   }
   double* dr = a.deriv + (size_t)pt * a.Dp;
@@ -626,7 +627,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_coop(DevMode
   DevModel m;
   CoopAux X;
   stage_model(mg, Xg, L, C, T, m, X);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // compile-time models: the model read from its global image (L1/L2 cached)
@@ -649,7 +650,7 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
   T.replay = a.nt_replay;
   SM m;
   m.bind(mg.img, mg);
-  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+  fd_fused_body(m, L, C, X, T, a, t - a.nB, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // The generic kernels' instances, instantiated here and in this order.  They
@@ -660,9 +661,9 @@ __global__ __launch_bounds__(TEAM, FD_WAVES_PER_EU) void k_fd_fused_g(DevModel m
 template __global__ void k_fd_centre_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int);
 template __global__ void k_fd_cols_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int);
 template __global__ void k_fd_fused_coop<>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused);
-template __global__ void k_fd_centre_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int, int);
-template __global__ void k_fd_cols_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int, int);
-template __global__ void k_fd_fused_coop<int>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused, int);
+template __global__ void k_fd_centre_coop<int, int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, double*, double*, int, int, int);
+template __global__ void k_fd_cols_coop<int, int>(DevModel, WsLayout, CoopLayout, CoopAux, TrajDev, int, const double*, const double*, CostDev, const double*, const double*, double*, int, int, int, int);
+template __global__ void k_fd_fused_coop<int, int>(DevModel, WsLayout, CoopLayout, CoopAux, FdFused, int, int);
 
 // ---- the fused sweep's ticket schedule (launch_fd_plan) -----------------
 // One 1024-thread workgroup.  Items: centre C(s,p) = p S + s (u < S P), column
@@ -806,7 +807,7 @@ size_t coop_lds_bytes(const WsLayout& L, const CoopLayout& C) {
 }
 
 // Each launch below: the grid and the LDS, then the bundled model's instance or
-// the generic kernel; cs... is the cost schedule's stride (SCH = int) or empty.
+// the generic kernel; cs... is the cost schedule's strides (SCH = int, int) or empty.
 template <class... SCH>
 static hipError_t fd_centre(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                             const FdArgs& a, SCH... cs) {
@@ -823,7 +824,7 @@ static hipError_t fd_centre(const DevModel& m, const WsLayout& L, const CoopLayo
 hipError_t launch_fd_centre_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                                  const FdArgs& a) {
   if (a.npts <= 0) return hipSuccess;
-  return a.cstride ? fd_centre(m, L, C, X, a, a.cstride) : fd_centre(m, L, C, X, a);
+  return a.cstride ? fd_centre(m, L, C, X, a, a.cstride, a.sstride) : fd_centre(m, L, C, X, a);
 }
 
 template <class... SCH>
@@ -845,7 +846,8 @@ hipError_t launch_fd_cols_coop(const DevModel& m, const WsLayout& L, const CoopL
   const int nctrl = m.nu < m.nv ? m.nu : m.nv;
   const long blocks = (long)a.npts * (nctrl + 2 * m.nv);
   if (blocks <= 0) return hipSuccess;
-  return a.cstride ? fd_cols(m, L, C, X, a, (unsigned)blocks, a.cstride) : fd_cols(m, L, C, X, a, (unsigned)blocks);
+  return a.cstride ? fd_cols(m, L, C, X, a, (unsigned)blocks, a.cstride, a.sstride)
+                   : fd_cols(m, L, C, X, a, (unsigned)blocks);
 }
 
 template <class... SCH>
@@ -863,11 +865,11 @@ static hipError_t fd_fused(const DevModel& m, const WsLayout& L, const CoopLayou
   return launch(k_fd_fused_coop<SCH...>, blocks, TEAM, lds, st, m, L, C, X, a, cs...);
 }
 hipError_t launch_fd_fused_coop(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
-                                const FdFused& a, hipStream_t st, int cstride) {
+                                const FdFused& a, hipStream_t st, int cstride, int sstride) {
   const long items = (long)a.S * a.P * (1 + (a.halves ? 2 : 1) * (a.nut + 2 * m.nv));
   const long blocks = items + a.nB;
   if (items <= 0) return hipSuccess;
-  return cstride ? fd_fused(m, L, C, X, a, (unsigned)blocks, st, cstride)
+  return cstride ? fd_fused(m, L, C, X, a, (unsigned)blocks, st, cstride, sstride)
                  : fd_fused(m, L, C, X, a, (unsigned)blocks, st);
 }
 

@@ -92,10 +92,14 @@ __device__ inline void load_state32(const DevModel& m, const WsLayout& L, const 
 
 // MT: DevModel, or DevModelNV<27> for 27-dof models (the humanoid: compile-time
 // sizes in the Newton Cholesky and its substitution, as the rollout's instance)
-// SCH: empty, or one int -- the instances launched while a cost schedule is set
-// (kernels.h cost_at), whose extra last argument is the schedule's row stride:
-// the point's costs are taken from its own row.  (A parameter pack and not a
+// SCH: empty, or two ints -- the instances launched while a cost schedule is set
+// (kernels.h cost_at), whose extra last arguments are the schedule's row stride
+// and its stride from seed to seed (sched_row): the point's costs are taken from
+// its own row of its seed's table.  (A parameter pack and not a
 // second body: the instances without a schedule keep the code they had.)
+__device__ inline CostDev sched_row(const CostDev& c, int pt, int P, int cstride, int sstride) {
+  return cost_at(c, pt / P, sstride, pt % P, cstride);
+}
 template <class MT, class... SCH>
 __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L, coop::CoopLayout C, coop::CoopAux X,
                                                         TrajDev tr, int P, const double* qfrc_applied,
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(TEAM32) void k_fd_centre32(DevModel mg, WsLayout L,
   T.replay = replay;
   STAMP_INIT();
   const int pt = blockIdx.x;
-  if constexpr (sizeof...(SCH) > 0) cost = cost_at(cost, pt % P, (cstride, ...));
+  if constexpr (sizeof...(SCH) > 0) cost = sched_row(cost, pt, P, cstride...);
   load_state32(m, L, T, tr, pt, pt / P, qfrc_applied, xfrc_applied);
   // every physics call inlined (FD32_INL): see k_fd_cols32
   FD32_INL forward_skip(m, L, C, X, T, STAGE_NONE, FD32_NITER, 0.0);
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(TEAM32) void k_fd_cols32(DevModel mg, WsLayout L, c
   const int nctrl = nu < nv ? nu : nv;  // mjderivative.cpp:78-82 (assumes nv >= nu)
   const int ncol = nctrl + 2 * nv;
   const int pt = blockIdx.x / ncol, col = blockIdx.x % ncol;
-  if constexpr (sizeof...(SCH) > 0) cost = cost_at(cost, pt % P, (cstride, ...));
+  if constexpr (sizeof...(SCH) > 0) cost = sched_row(cost, pt, P, cstride...);
   double* dr = deriv + (size_t)pt * Ds;
   const double* wc = warm_c + (size_t)pt * nv;
   const float costCenter = (float)cost_c[pt];
@@ -211,7 +215,7 @@ size_t coop_lds_bytes_f32(const WsLayout& L, const coop::CoopLayout& C) {
   return (size_t)(L.nd + C.nd) * sizeof(float) + (size_t)(L.ni + C.ni) * sizeof(int);
 }
 
-// cs...: the cost schedule's stride (SCH = int) or empty
+// cs...: the cost schedule's strides (SCH = int, int) or empty
 template <class... SCH>
 static hipError_t fd_sweep32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C, const coop::CoopAux& X,
                              const FdArgs& a, float eps, SCH... cs) {
@@ -232,7 +236,8 @@ static hipError_t fd_sweep32(const DevModel& m, const WsLayout& L, const coop::C
 hipError_t launch_fd_sweep_f32(const DevModel& m, const WsLayout& L, const coop::CoopLayout& C,
                                const coop::CoopAux& X, const FdArgs& a, double eps) {
   if (a.npts <= 0) return hipSuccess;
-  return a.cstride ? fd_sweep32(m, L, C, X, a, (float)eps, a.cstride) : fd_sweep32(m, L, C, X, a, (float)eps);
+  return a.cstride ? fd_sweep32(m, L, C, X, a, (float)eps, a.cstride, a.sstride)
+                   : fd_sweep32(m, L, C, X, a, (float)eps);
 }
 
 }  // namespace ilqg

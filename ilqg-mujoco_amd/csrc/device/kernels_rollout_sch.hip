@@ -1,5 +1,5 @@
 // The rollout kernels of a solver with a cost schedule
-// (ilqg_solver_set_cost_schedule): the <.., int> instances of k_rollout2_s and
+// (ilqg_solver_set_cost_schedule): the <.., int, int> instances of k_rollout2_s and
 // k_rollout2_coop (rollout_body.h) -- point n charged with row n of the
 // schedule, the LDS cost copy re-staged per point from a row prefetched into
 // registers -- each with and without the control-limit clamp.  A unit of its
@@ -11,7 +11,8 @@ namespace ilqg {
 
 hipError_t launch_rollout_sch(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                               const RollArgs& a, bool lim) {
-  return lim ? launch_rollout2<true>(m, L, C, X, a, a.cstride) : launch_rollout2<false>(m, L, C, X, a, a.cstride);
+  return lim ? launch_rollout2<true>(m, L, C, X, a, a.cstride, a.sstride)
+             : launch_rollout2<false>(m, L, C, X, a, a.cstride, a.sstride);
 }
 
 }  // namespace ilqg

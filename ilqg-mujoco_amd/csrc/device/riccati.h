@@ -808,10 +808,10 @@ __device__ inline void backward_seed(const MD& m, int nq, int nv_rt, int nu_rt, 
     luu = lxx + nx;
     dl = luu + nu;  // std_lds_doubles(nv, nu) further on
   }
-  // STD: lxx, luu of point p's cost row
+  // STD: lxx, luu of point p's cost row (of seed s's table: sd.sstride)
   auto hess = [&](int p) {
     if constexpr (STD) {
-      const CostDev cr = cost_at(sd.cost, p, sd.cstride);
+      const CostDev cr = cost_at(sd.cost, s, sd.sstride, p, sd.cstride);
       for (int i = tid; i < nx; i += BW_THREADS) lxx[i] = 2 * (i < nv ? cr.wq[i] : cr.wv[i - nv]);
       for (int a = tid; a < nu; a += BW_THREADS) luu[a] = 2 * cr.wu[a];
     }

@@ -39,12 +39,13 @@ hipError_t launch_rollout_sch(const DevModel& m, const WsLayout& L, const coop::
 namespace {
 
 __device__ inline void rollout_body(const auto& m, const auto& L, const auto& C, const auto& X, const Team& T,
-                                int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, int wave, auto split, auto lowreg, auto clamp, auto sched, int cstride = 0) {
+                                int S, int A, int P, TrajDev nom, TrajDev out, int out_is_cand, const double* K, const double* k, const double* alphas, TrajDev dinit, const double* qfrc_applied, const double* xfrc_applied, int passive, CostDev cost, double* cost_cand, RollChunk ch, int wave, auto split, auto lowreg, auto clamp, auto sched, int cstride = 0, int sstride = 0) {
   // clamp (the kernels' LIM instances, launched while control limits are set):
   // the control law's output confined to [ch.ulim[i], ch.ulim[nu + i]]
-  // sched (their <.., int> instances, launched while a cost schedule is set):
-  // point n is charged with row n of the schedule, cost.wq + n cstride, which
-  // is packed as stage_cost lays the LDS copy out (wq tq lq wv tv lv wu tu lu)
+  // sched (their <.., int, int> instances, launched while a cost schedule is set):
+  // point n is charged with row n of the seed's schedule, cost.wq + s sstride +
+  // n cstride (sstride = 0: one table for every seed), which is packed as
+  // stage_cost lays the LDS copy out (wq tq lq wv tv lv wu tu lu)
   // wave < 0: one-wave team; 0/1: primary/helper wave of a two-wave team (step_dual)
   const bool prim = wave <= 0;
   STAMP_INIT();
@@ -61,6 +62,7 @@ __device__ inline void rollout_body(const auto& m, const auto& L, const auto& C,
   else load_state(m, L, T, dinit, s, s, qfrc_applied, xfrc_applied);
   // (a resumed chunk of a scheduled rollout stages row n_hi, not row 0)
   constexpr bool SCH = decltype(sched)::value;
+  if constexpr (SCH) cost = cost_at(cost, s, sstride);  // the seed's table (cost.wq: its row 0)
   const CostDev cl = stage_cost(m, C, T, [&] {
     if constexpr (SCH) return cost_at(cost, nhi, cstride);
     else return cost;
@@ -310,8 +312,8 @@ inline size_t rollout_lds(size_t need) {
 }
 
 // ---- the default rollout kernels.  LIM: the control law clamped to the
-// solver's control limits (RollChunk.ulim); SCH...: a cost schedule's row
-// stride (coop_common.h).  Each unit instantiates the ones it launches.
+// solver's control limits (RollChunk.ulim); SCH...: a cost schedule's two
+// strides (coop_common.h).  Each unit instantiates the ones it launches.
 // two-wave teams (step_dual): 128 threads per (seed, candidate).  MT: DevModel,
 // or DevModelNV<27> for 27-dof models (the humanoid: compile-time sizes in the
 // Newton Cholesky and its substitution)
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(2 * TEAM) void k_rollout2_coop(DevModel mg, WsLayou
   stage_model(mg, Xg, L, C, T, m, X);
   rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
                passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::false_type{}, std::true_type{},
-               std::bool_constant<LIM>{}, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...));
+               std::bool_constant<LIM>{}, std::bool_constant<(sizeof...(SCH) > 0)>{}, sched_stride(cstride...), sched_seed(cstride...));
 }
 // three-wave teams for the compile-time register-row models (rollout_waves)
 template <class SM, class SX, bool LIM, class... SCH>
@@ -337,7 +339,7 @@ __global__ __launch_bounds__(3 * TEAM) void k_rollout2_s(DevModel mg, int S, int
   rollout_body(m, L, C, X, T, S, A, P, nom, out, out_is_cand, K, k, alphas, dinit, qfrc_applied, xfrc_applied,
                passive, cost, cost_cand, ch, (int)(threadIdx.x / TEAM), std::bool_constant<SM::nv <= RMAX>{},
                std::false_type{}, std::bool_constant<LIM>{}, std::bool_constant<(sizeof...(SCH) > 0)>{},
-               sched_stride(cstride...));
+               sched_stride(cstride...), sched_seed(cstride...));
 }
 
 // the second buffer of the generic kernel's record, past the workspace when it
@@ -358,7 +360,7 @@ inline size_t rollout_dbuf_lds(const DevModel& m, const WsLayout& L, const CoopL
 }
 
 // launch of the default kernels: the bundled model's k_rollout2_s, or
-// k_rollout2_coop; cs... is the cost schedule's stride (SCH = int) or empty
+// k_rollout2_coop; cs... is the cost schedule's strides (SCH = int, int) or empty
 template <bool LIM, class... SCH>
 hipError_t launch_rollout2(const DevModel& m, const WsLayout& L, const CoopLayout& C, const CoopAux& X,
                            const RollArgs& a, SCH... cs) {

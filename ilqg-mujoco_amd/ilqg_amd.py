@@ -71,6 +71,8 @@ EXPORTS = [
     "ilqg_solver_point_owners",
     "ilqg_model_ctrlrange", "ilqg_solver_set_ctrl_limits", "ilqg_solver_get_ctrl_limits", "ilqg_solver_get_clamped",
     "ilqg_solver_set_cost_schedule", "ilqg_solver_get_cost_schedule", "ilqg_solver_shift_cost_schedule",
+    "ilqg_solver_set_cost_schedule_seeds", "ilqg_solver_get_cost_schedule_seeds",
+    "ilqg_solver_shift_cost_schedule_seeds",
     "ilqg_solver_set_recursion", "ilqg_solver_get_expected",
     "ilqg_solver_set_regularization", "ilqg_solver_get_regularization", "ilqg_solver_get_reg_state",
     "ilqg_solver_set_reg_mu", "ilqg_solver_get_reg_trace",
@@ -611,6 +613,55 @@ class ILQR:
         if n >= 1 and new_rows.shape[0] != n:
             raise IlqgError(f"shift_cost_schedule: {n} steps need {n} new rows, got {new_rows.shape[0]}")
         _check(lib().ilqg_solver_shift_cost_schedule(self._h, n, _ptr(new_rows)), "shift_cost_schedule")
+
+    def _cost_rows_seeds(self, rows, n=None):
+        """per-seed rows as an (S, n, C) float64 array: such an array, or S
+        sequences of packed rows / Costs"""
+        if isinstance(rows, np.ndarray) and rows.ndim == 3:
+            per = [rows[s] for s in range(rows.shape[0])]
+        else:
+            per = list(rows)
+        if len(per) != self.S:
+            raise IlqgError(f"per-seed cost rows: {self.S} seeds, got {len(per)} tables")
+        return np.ascontiguousarray(np.stack([self._cost_rows(r, n) for r in per]))
+
+    def set_cost_schedule_seeds(self, rows):
+        """per-seed cost schedule (ilqg_solver_set_cost_schedule_seeds): seed
+        s's point p is charged with rows[s][p] -- every seed tracks a reference
+        of its own.  rows: an (S, N+1, C) array, S tables as set_cost_schedule
+        takes them, or None to switch every schedule off.  Replaces a shared
+        schedule; set_cost_schedule replaces this one."""
+        if rows is None:
+            _check(lib().ilqg_solver_set_cost_schedule_seeds(self._h, None), "set_cost_schedule_seeds")
+            return
+        rows = self._cost_rows_seeds(rows, self.P)
+        _check(lib().ilqg_solver_set_cost_schedule_seeds(self._h, _ptr(rows)), "set_cost_schedule_seeds")
+
+    def cost_schedule_seeds(self):
+        """(rows, per_seed): every seed's (N+1, C) rows in force as an
+        (S, N+1, C) array -- the shared rows or the creation cost repeated while
+        no per-seed table is set -- and whether one is
+        (ilqg_solver_get_cost_schedule_seeds)"""
+        m = self.model
+        rows = np.zeros((self.S, self.P, 3 * (m.nq + m.nv + m.nu)))
+        per = ctypes.c_int(0)
+        _check(lib().ilqg_solver_get_cost_schedule_seeds(self._h, _ptr(rows), ctypes.byref(per)),
+               "get_cost_schedule_seeds")
+        return rows, bool(per.value)
+
+    def shift_cost_schedule_seeds(self, n, new_rows):
+        """the per-seed receding-horizon tick
+        (ilqg_solver_shift_cost_schedule_seeds): every seed's window advances n
+        steps and its rows 0 .. n-1 take new_rows[s] (an (S, n, C) array or S
+        sequences of n rows / Costs)"""
+        n = int(n)
+        if new_rows is None:
+            _check(lib().ilqg_solver_shift_cost_schedule_seeds(self._h, n, None), "shift_cost_schedule_seeds")
+            return
+        new_rows = self._cost_rows_seeds(new_rows)
+        if n >= 1 and new_rows.shape[1] != n:
+            raise IlqgError(f"shift_cost_schedule_seeds: {n} steps need {n} new rows per seed, got {new_rows.shape[1]}")
+        _check(lib().ilqg_solver_shift_cost_schedule_seeds(self._h, n, _ptr(new_rows)), "shift_cost_schedule_seeds")
 
     def shift_horizon(self, n: int = 1, tail="hold"):
         """the receding-horizon tick of the nominal (ilqg_solver_shift_horizon;

@@ -14,6 +14,10 @@ own stream (or the one given to ILQR.set_stream).  CostExchange, given the
 solver, makes torch's current stream wait on the solver's launch stream before
 every gather, so the costs it reads are the ones the last iterate() wrote --
 whichever stream the solver runs on.  No host round trip is involved.
+
+Per-seed cost schedules (ILQR.set_cost_schedule_seeds) are per solver: a rank
+passes the rows of the seeds it owns, rows[seed_offset(rank, S) : +S] of the
+global table, to its own solver.
 """
 import torch
 import torch.distributed as dist

@@ -255,7 +255,8 @@ int ilqg_solver_get_ctrl_limits(ilqg_solver* s, double* lo, double* hi, int* ena
    Synchronises.  No counterpart in the reference. */
 int ilqg_solver_get_clamped(ilqg_solver* s, unsigned* mask, unsigned* info);
 /* Cost schedule: one cost row per trajectory point, resident on the device and
-   shared by every seed; off by default.  No counterpart in the reference: it
+   shared by every seed (ilqg_solver_set_cost_schedule_seeds below: a table per
+   seed); off by default.  No counterpart in the reference: it
    stands in for a stepCostFn_t (inc/mjderivative.h:5) that reads d->time, i.e.
    a running cost that moves over the horizon, and a terminal cost of its own.
    rows: (N+1) x C doubles, C = 3 (nq + nv + nu); row p, the cost of point p, is
@@ -276,18 +277,52 @@ int ilqg_solver_get_clamped(ilqg_solver* s, unsigned* mask, unsigned* info);
    fp32 FD, the MFMA engine, seed groups (every group reads the same rows) and
    ilqg_forward_sharded.  ILQG_ERR_UNSUPPORTED, from whichever call comes
    second: from the forward calls when ILQG_DUAL=0 selects a rollout kernel
-   without a scheduled variant. */
+   without a scheduled variant.
+   On a solver with a per-seed schedule this call replaces it by the shared
+   one, and NULL switches it off. */
 int ilqg_solver_set_cost_schedule(ilqg_solver* s, const double* rows);
 /* the rows in force, (N+1) x C, and whether a schedule is on; either pointer
    may be NULL.  While off every row reads as the creation cost.  No counterpart
-   in the reference (it stands in for reading back such a stepCostFn_t's state). */
+   in the reference (it stands in for reading back such a stepCostFn_t's state).
+   While a per-seed schedule is in force enabled reads 1 and a non-NULL rows is
+   ILQG_ERR_ARG: there is no single table to return. */
 int ilqg_solver_get_cost_schedule(ilqg_solver* s, double* rows, int* enabled);
 /* the receding-horizon tick of a schedule: the window advances n steps, row p
    takes row p - n for p >= n and rows 0 .. n-1 take new_rows (n x C).  No
    counterpart in the reference: a stepCostFn_t that reads d->time follows the
    advancing clock by itself.  ILQG_ERR_ARG while the schedule is off, for
-   n < 1 or n > N+1, and for new_rows NULL or non-finite.  Synchronises. */
+   n < 1 or n > N+1, and for new_rows NULL or non-finite.  Synchronises.
+   While a per-seed schedule is in force every seed's table advances and takes
+   the same n new rows. */
 int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_rows);
+/* Per-seed cost schedule: every seed, an MPC problem of its own, tracks a
+   reference of its own.  rows: nseed x (N+1) x C doubles, seed s's table at
+   rows + s (N+1) C; the row packing and the point indexing are those of
+   ilqg_solver_set_cost_schedule, row [s][0] is seed s's terminal cost.  It
+   replaces a shared schedule if one is set; NULL switches every schedule off
+   (the solver is then exactly as created); a non-finite entry is ILQG_ERR_ARG.
+   Synchronises like ilqg_solver_set_mu, invalidates the regularisation mode's
+   nominal cost, and keeps two nseed x (N+1) x C tables on the device.
+   Everywhere a shared schedule reads row p, seed s now reads row [s][p]: the
+   rollout, every FD sweep (fused, unfused, ilqg_fd_sweep_range, fp32, the tail
+   records of ilqg_solver_shift_horizon) and the STANDARD recursion's lxx / luu,
+   with s the solver's seed index in every launch -- a seed group reads its own
+   seeds' rows, and under ilqg_forward_sharded every rank holds the full table.
+   Composes with whatever the shared schedule composes with, the same
+   ILQG_DUAL=0 refusal included; the constructor's passive rollout,
+   ilqg_fd_batch and the legacy layer keep the creation cost.  No counterpart
+   in the reference. */
+int ilqg_solver_set_cost_schedule_seeds(ilqg_solver* s, const double* rows);
+/* every seed's rows in force, nseed x (N+1) x C, and whether a per-seed table
+   is in force; either pointer may be NULL.  per_seed = 0 with a shared
+   schedule (each seed's block then reads as the shared rows) and while off
+   (each block reads as the creation cost). */
+int ilqg_solver_get_cost_schedule_seeds(ilqg_solver* s, double* rows, int* per_seed);
+/* the per-seed receding-horizon tick: for every seed s, row [s][p] takes row
+   [s][p - n] for p >= n and rows [s][0 .. n-1] take new_rows[s] (new_rows:
+   nseed x n x C).  The argument checks of ilqg_solver_shift_cost_schedule;
+   ILQG_ERR_ARG unless a per-seed table is in force.  Synchronises. */
+int ilqg_solver_shift_cost_schedule_seeds(ilqg_solver* s, int n, const double* new_rows);
 /* Horizon shift: the receding-horizon tick of the nominal trajectory, the gains
    and the FD records, on the device.  The reference has no counterpart: its
    driver reuses dArray unshifted as the next nominal.  Per seed,
@@ -306,8 +341,9 @@ int ilqg_solver_shift_cost_schedule(ilqg_solver* s, int n, const double* new_row
    3. tail records: the FD records of points 0 .. n-1 are swept behind the
       tail on the same stream, by the kernels of ilqg_fd_sweep_range(s, 0, n)
       launched once for every seed (the same records): the FD precision that
-      is set and the cost rows in force at that moment -- with a schedule
-      the tick is ilqg_solver_shift_cost_schedule, then this call, and a moved
+      is set and the cost rows in force at that moment, seed by seed -- with a
+      schedule the tick is ilqg_solver_shift_cost_schedule (or its _seeds
+      form), then this call, and a moved
       record is still the record of its point under its row;
    4. dinit takes new point N, the nominal's prediction of "now", so that
       ilqg_iterate can follow with no host call; a later ilqg_solver_set_dinit
