@@ -297,6 +297,9 @@ struct ilqg_solver {
   // launch and one sweep launch for all seeds, then stored into the resident
   // arrays (sized for n = N)
   DevBuf shift_tail[5], shift_rec;
+  // ilqg_solver_refresh_nominal(REROLL): the one feed-forward scale of its
+  // rollout, a zero on the device (first call allocates)
+  DevBuf zero_alpha;
   // seed groups (ilqg_solver_set_groups): the seeds as G contiguous ranges,
   // software-pipelined.  Group g has a rollout stream (CU-masked to an XCD of
   // its own: one rollout workgroup per CU) and a sweep stream (every CU but the
@@ -1511,6 +1514,57 @@ int ilqg_solver_shift_horizon(ilqg_solver* s, int n, int tail) {
   // stream, unlike reg_invalidate: nothing here waits for the device)
   s->cl_valid = false;
   if (s->reg_on) HIPCHK(hipMemsetAsync(s->reg_valid.p, 0, s->reg_valid.n, s->stream));
+  return ILQG_OK;
+}
+
+// The nominal's cost made valid again, on the solver's stream and nothing else.
+// COST: one launch, k_nominal_cost over the stored trajectory.  REROLL: the
+// rollout launch of a one-candidate solver -- A = 1, the feed-forward scale a
+// device zero, the nominal written in place, the candidate's cost straight into
+// the selected-cost buffer -- then k_nominal_cost's epilogue (setDInit and the
+// regularisation state; the cost is the rollout's own).
+int ilqg_solver_refresh_nominal(ilqg_solver* s, int mode, unsigned flags) {
+  if (!s || !s->initialized) return fail(ILQG_ERR_ARG, "solver not initialised");
+  if (mode != ILQG_NOMINAL_COST && mode != ILQG_NOMINAL_REROLL)
+    return fail(ILQG_ERR_ARG, "refresh_nominal: mode must be ILQG_NOMINAL_COST or ILQG_NOMINAL_REROLL");
+  if (flags & ~ILQG_NOMINAL_RESUME) return fail(ILQG_ERR_ARG, "refresh_nominal: unknown flag");
+  const bool resume = (flags & ILQG_NOMINAL_RESUME) != 0;
+  if (resume && !s->reg_on)
+    return fail(ILQG_ERR_ARG, "refresh_nominal: ILQG_NOMINAL_RESUME needs the regularisation mode");
+  const bool reroll = mode == ILQG_NOMINAL_REROLL;
+  if (reroll)
+    if (int rc = limits_rollout_check(s)) return rc;
+  const ilqg_model* m = s->model;
+  const HostModel& h = m->host;
+  const TrajDev nom = s->tview(s->traj), di = s->tview(s->dinit);
+  if (reroll && !s->zero_alpha.p) {
+    // (zeroed on the solver's stream, as shift_horizon's buffers are)
+    HIPCHK(hipMalloc(&s->zero_alpha.p, 8));
+    s->zero_alpha.n = 8;
+    HIPCHK(hipMemsetAsync(s->zero_alpha.p, 0, 8, s->stream));
+  }
+  s->grp_join = true;
+  if (reroll) {
+    RollChunk ch;
+    if (s->limits) ch.ulim = s->ulim.as<double>();
+    HIPCHK(s->timed(0, [&] {
+      return launch_rollout_coop(m->dm, m->Lc, m->C, m->X,
+                                 RollArgs{s->S, 1, s->P, nom, nom, 0, s->K.as<double>(), s->k.as<double>(),
+                                          s->zero_alpha.as<double>(), di, s->qfrc_applied.as<double>(),
+                                          s->xfrc_applied.as<double>(), 0, s->cview(), s->cost_sel.as<double>(),
+                                          s->stream, ch, s->cstride(), s->sstride()});
+    }));
+  }
+  NomCostArgs a{h.nq, h.nv, h.nu, s->S, s->P, nom};
+  if (reroll) a.dinit = di;
+  a.cost = s->cview();
+  a.cstride = s->cstride();
+  a.sstride = s->sstride();
+  a.cost_sel = s->cost_sel.as<double>();
+  a.compute = reroll ? 0 : 1;
+  a.resume = resume ? 1 : 0;
+  if (s->reg_on) a.rg = s->rview(-1);
+  HIPCHK(s->timed(1, [&] { return launch_nominal_cost(a, s->stream); }));
   return ILQG_OK;
 }
 

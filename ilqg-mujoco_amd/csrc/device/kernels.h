@@ -204,6 +204,28 @@ struct ShiftArgs {
 hipError_t launch_shift_horizon(const ShiftArgs& a, hipStream_t st);
 hipError_t launch_shift_store(const ShiftArgs& a, hipStream_t st);
 
+// Nominal refresh (ilqg_solver_refresh_nominal; kernels_shift.hip k_nominal_cost),
+// one workgroup per seed.  compute = 1: the cost of the nominal trajectory nom,
+// [S][P] points, under the rows in force -- seed s, point n:
+// cost_at(cost, s, sstride, n, cstride), both strides 0 for the creation cost
+// -- summed exactly as the rollout charges a candidate, into cost_sel[s].
+// compute = 0: cost_sel[s] already holds that cost (a rollout wrote it) and
+// dinit takes point N of nom.  Either way, when rg.cost_nom is set (the
+// regularisation mode): cost_nom[s] = that cost, valid[s] = 1, and with
+// resume a status of 1 becomes 0.
+struct NomCostArgs {
+  int nq, nv, nu, S, P;
+  TrajDev nom;
+  TrajDev dinit{};  // compute = 0 only
+  CostDev cost{};
+  int cstride = 0, sstride = 0;
+  double* cost_sel = nullptr;
+  int compute = 1;
+  int resume = 0;
+  RegDev rg{};
+};
+hipError_t launch_nominal_cost(const NomCostArgs& a, hipStream_t st);
+
 // fused FD sweep + streamed backward pass (kernels_fd.hip)
 struct FdFused {
   TrajDev tr;

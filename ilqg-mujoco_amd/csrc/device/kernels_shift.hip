@@ -3,7 +3,11 @@
 // rollout kernels' (kernels_rollout.hip, a rollout of horizon n from
 // ShiftArgs.carry) and its records are the two-kernel FD sweep's: this unit has
 // no physics.
-#include "kernels.h"
+// Nominal refresh (ilqg_solver_refresh_nominal): the cost of the stored nominal
+// under the rows in force, summed as the rollout sums it (k_nominal_cost).
+// coop_common.h is included for step_cost alone -- the one definition the
+// rollout charges with; none of its physics is instantiated here.
+#include "coop_common.h"
 
 namespace ilqg {
 namespace {
@@ -68,7 +72,75 @@ __global__ __launch_bounds__(SHIFT_THREADS) void k_shift_store(ShiftArgs a) {
   for (int p = 0; p < n; p++) dst[(size_t)p * W] = src[(size_t)p * W];
 }
 
+// points a workgroup of k_nominal_cost charges per pass: the LDS it holds, whatever P is
+constexpr int NOMC_TILE = 256;
+
+// One workgroup per seed.  a.compute: thread i of a pass takes point hi - i and
+// forms its subtotal exactly as the rollout does, step_cost from 0 in (q, v, u)
+// order under row (s, n); the subtotals go to LDS and thread 0 adds them to c
+// in the rollout's order n = N, N-1, .., 0 (rollout_body.h: c = 0; c +=
+// step_cost(point n)), carrying c from one pass of NOMC_TILE points to the next:
+// the same additions on the same operands, so the same bits.  !a.compute
+// (behind a rollout that charged the nominal into cost_sel itself): c is that
+// cost, and dinit takes point N as the selection's setDInit does.
+// Thread 0 then publishes: the selected cost, and in the regularisation mode
+// cost_nom, valid = 1 and -- a.resume -- status 1 -> 0.
+__global__ __launch_bounds__(NOMC_TILE) void k_nominal_cost(NomCostArgs a) {
+  __shared__ double sub[NOMC_TILE];
+  const int s = blockIdx.x, t = threadIdx.x, N = a.P - 1;
+  const int nq = a.nq, nv = a.nv, nu = a.nu;
+  double c = 0;
+  if (a.compute) {
+    const struct { int nq, nv, nu; } m{nq, nv, nu};
+    for (int hi = N; hi >= 0; hi -= NOMC_TILE) {
+      const int n = hi - t;
+      if (n >= 0) {
+        const size_t pt = (size_t)s * a.P + n;
+        sub[t] = step_cost(m, cost_at(a.cost, s, a.sstride, n, a.cstride), a.nom.qpos + pt * nq, a.nom.qvel + pt * nv,
+                           a.nom.ctrl + pt * nu);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const int cnt = hi + 1 < NOMC_TILE ? hi + 1 : NOMC_TILE;
+        for (int i = 0; i < cnt; i++) c += sub[i];
+      }
+      __syncthreads();
+    }
+  } else {
+    if (t == 0) c = a.cost_sel[s];
+    // setDInit(dArray[N]), inc/ilqr.h:183
+    const size_t sp = (size_t)s * a.P + N;
+    if (t == 0) a.dinit.time[s] = a.nom.time[sp];
+    for (int i = t; i < nq; i += NOMC_TILE) a.dinit.qpos[(size_t)s * nq + i] = a.nom.qpos[sp * nq + i];
+    for (int i = t; i < nv; i += NOMC_TILE) {
+      a.dinit.qvel[(size_t)s * nv + i] = a.nom.qvel[sp * nv + i];
+      a.dinit.warm[(size_t)s * nv + i] = a.nom.warm[sp * nv + i];
+    }
+    for (int i = t; i < nu; i += NOMC_TILE) a.dinit.ctrl[(size_t)s * nu + i] = a.nom.ctrl[sp * nu + i];
+  }
+  if (t != 0) return;
+  if (a.compute) a.cost_sel[s] = c;
+  if (a.rg.cost_nom) {
+    a.rg.cost_nom[s] = c;
+    a.rg.valid[s] = 1;
+    if (a.resume && a.rg.status[s] == 1) a.rg.status[s] = 0;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_nominal_cost(const NomCostArgs& a, hipStream_t st) {
+  if (a.S < 1 || a.P < 1 || a.nq < 1 || a.nv < 1 || a.nu < 0 || !a.cost_sel || !a.nom.qpos || !a.nom.qvel ||
+      !a.nom.ctrl)
+    return hipErrorInvalidValue;
+  if (a.compute && !a.cost.wq) return hipErrorInvalidValue;
+  if (!a.compute && (!a.nom.time || !a.nom.warm || !a.dinit.time || !a.dinit.qpos || !a.dinit.qvel ||
+                     !a.dinit.warm || !a.dinit.ctrl))
+    return hipErrorInvalidValue;
+  if (a.rg.cost_nom && (!a.rg.valid || !a.rg.status)) return hipErrorInvalidValue;
+  if (a.resume && !a.rg.cost_nom) return hipErrorInvalidValue;
+  return launch(k_nominal_cost, (unsigned)a.S, (unsigned)NOMC_TILE, 0, st, a);
+}
 
 hipError_t launch_shift_store(const ShiftArgs& a, hipStream_t st) {
   if (a.S < 1 || a.P < 2 || a.n < 1 || a.n > a.P - 1) return hipErrorInvalidValue;

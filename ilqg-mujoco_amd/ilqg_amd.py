@@ -76,9 +76,11 @@ EXPORTS = [
     "ilqg_solver_set_recursion", "ilqg_solver_get_expected",
     "ilqg_solver_set_regularization", "ilqg_solver_get_regularization", "ilqg_solver_get_reg_state",
     "ilqg_solver_set_reg_mu", "ilqg_solver_get_reg_trace",
-    "ilqg_solver_shift_horizon",
+    "ilqg_solver_shift_horizon", "ilqg_solver_refresh_nominal",
 ]
 TAIL_MODES = {"hold": 0}  # ILQG_TAIL_HOLD
+NOMINAL_MODES = {"cost": 0, "reroll": 1}  # ILQG_NOMINAL_COST, ILQG_NOMINAL_REROLL
+NOMINAL_RESUME = 1  # ILQG_NOMINAL_RESUME
 REG_MAXRETRY, REG_MAXTRACE, REG_TRACE = 16, 1024, 8
 REG_TRACE_FIELDS = ("cost_nom", "cost_best", "chosen", "expected", "mu_before", "mu_accept", "mu_backward", "code")
 
@@ -139,6 +141,8 @@ def lib() -> ctypes.CDLL:
         L.ilqg_solver_stream.restype = ctypes.c_void_p
         L.ilqg_solver_shift_horizon.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.ilqg_solver_shift_horizon.restype = ctypes.c_int
+        L.ilqg_solver_refresh_nominal.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint]
+        L.ilqg_solver_refresh_nominal.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -676,6 +680,22 @@ class ILQR:
                 raise IlqgError(f"shift_horizon: tail must be one of {sorted(TAIL_MODES)}")
             tail = TAIL_MODES[tail]
         _check(lib().ilqg_solver_shift_horizon(self._h, int(n), int(tail)), "shift_horizon")
+
+    def refresh_nominal(self, mode: str = "cost", resume: bool = False):
+        """the nominal's cost made valid again on the device
+        (ilqg_solver_refresh_nominal; the reference keeps no trajectory cost):
+        'cost' charges the stored nominal under the cost rows in force, exactly
+        as the rollout charged it; 'reroll' first rolls the stored policy out
+        from dinit with feed-forward scale 0 and makes that the nominal (after
+        set_dinit(measured state)).  The selected cost is rewritten, and in the
+        regularisation mode cost_nom with valid = 1, so that the next
+        forward_pass() tests its step; resume=True also sets a converged seed
+        (status 1) running again.  Enqueued on the solver's stream, no host
+        sync: the tick is shift_horizon(n); refresh_nominal(); iterate()."""
+        if mode not in NOMINAL_MODES:
+            raise IlqgError(f"refresh_nominal: mode must be one of {sorted(NOMINAL_MODES)}")
+        _check(lib().ilqg_solver_refresh_nominal(self._h, NOMINAL_MODES[mode], NOMINAL_RESUME if resume else 0),
+               "refresh_nominal")
 
     def set_groups(self, ngroups: int):
         """seed groups (ilqg_solver_set_groups): iterate() software-pipelines

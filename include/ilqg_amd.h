@@ -356,8 +356,9 @@ int ilqg_solver_shift_cost_schedule_seeds(ilqg_solver* s, int n, const double* n
    points itself.  Stale by construction afterwards: ilqg_solver_get_value and
    ilqg_solver_get_costs keep the last pass's values, ilqg_solver_get_clamped
    reads 0 until the next boxed pass, and in the regularisation mode the nominal
-   cost is invalid (mu, dmu, status and the trace are untouched; the shifted
-   nominal's cost is not recomputed on the device).  With ilqg_solver_set_timing
+   cost is invalid (mu, dmu, status and the trace are untouched;
+   ilqg_solver_refresh_nominal recomputes the shifted nominal's cost on the
+   device and makes it valid again).  With ilqg_solver_set_timing
    the move and the tail's store count under index 1, the tail's rollout under
    0, the tail sweep under 3.
    ILQG_ERR_ARG: s NULL or not initialised, n < 1, n > N, tail not
@@ -366,6 +367,54 @@ int ilqg_solver_shift_cost_schedule_seeds(ilqg_solver* s, int n, const double* n
    MFMA engine and seed groups, and changes no refusal. */
 #define ILQG_TAIL_HOLD 0
 int ilqg_solver_shift_horizon(ilqg_solver* s, int n, int tail);
+/* Nominal refresh: the stored nominal trajectory's cost, valid again on the
+   device -- what the regularisation mode's accept test needs after a
+   receding-horizon tick, where every step is the first one after a shift.  The
+   reference has no counterpart: its forwardPass (inc/ilqr.h:116-130) keeps no
+   trajectory cost and accepts every step.  Works with the regularisation mode
+   on or off.  Enqueued on the solver's stream: no synchronisation, nothing
+   copied to or from the host (REROLL's first call allocates one double,
+   zeroed in stream).
+   ILQG_NOMINAL_COST: per seed s, the cost of the stored nominal under the cost
+   rows in force at that moment -- row [s][n] of a per-seed schedule, row n of a
+   shared one, else the creation cost -- summed exactly as the rollout charges
+   a candidate: c = 0; for n = N .. 0: c += step_cost(row n; qpos_n, qvel_n,
+   ctrl_n), a point's terms in ilqg_cost's order.  It is, bit for bit, what
+   ilqg_forward wrote for the candidate that became this nominal.  Written to
+   the selected-cost buffer (ilqg_solver_device_costs) always, and in the
+   regularisation mode to cost_nom[s] with valid[s] = 1.  Untouched: the
+   trajectory, dinit, the gains, the FD records, the selection and the
+   candidate costs (ilqg_solver_get_costs), dV, mu, dmu, retries and the trace
+   (it does not advance).
+   ILQG_NOMINAL_REROLL: the stored policy rolled out from dinit with
+   feed-forward scale 0, u_n = K_n (x_n - x*_n) + 0 k_n + u*_n, clamped while
+   control limits are on, charged under the rows in force, the seed's applied
+   forces applied; the result becomes the nominal unconditionally.  Every array
+   comes out as ilqg_forward leaves it on a solver created with nalpha = 1,
+   alphas = {0.0}, select_mode = 0 and given the same nominal, gains and dinit:
+   the trajectory's five fields, dinit (= new point N) and the selected cost,
+   bit for bit; then cost_nom / valid as under COST.  The gains stay; the FD
+   records are now those of the old nominal -- ilqg_iterate sweeps again behind
+   its own rollout, ilqg_backward alone would read stale records.  The
+   ILQG_DUAL=0 refusals of the forward calls apply.  After
+   ilqg_solver_set_dinit(measured state) this is the nominal the accept test
+   must compare against.
+   ILQG_NOMINAL_RESUME (a flag, with COST or REROLL; needs the regularisation
+   mode on): a seed
+   whose status is 1 (converged on the window that has moved on) runs again,
+   status 0; status 2, mu and dmu stay.  Without the flag the status is kept.
+   ILQG_ERR_ARG, nothing changed: s NULL or not initialised, an unknown mode or
+   flag bit, RESUME while the regularisation mode is off.
+   Seed groups wait for it as for ilqg_solver_shift_horizon; under
+   ilqg_forward_sharded every rank calls it identically.  With
+   ilqg_solver_set_timing the cost kernel counts under index 1, REROLL's
+   rollout under 0.  Composes with both layouts and recursions, control limits,
+   both cost schedules, fp32 FD, the MFMA engine, seed groups and models with
+   nq != nv, and lifts no refusal. */
+#define ILQG_NOMINAL_COST 0
+#define ILQG_NOMINAL_REROLL 1
+#define ILQG_NOMINAL_RESUME 1u
+int ilqg_solver_refresh_nominal(ilqg_solver* s, int mode, unsigned flags);
 /* Recursion mode.  REFERENCE (default): the backward step of inc/ilqr.h:157-174
    as the reference wrote it (outer products of the FD cost gradients for
    Hessians, mu added to V and kept, factors of 2: SURVEY.md Appendix A Q13,
@@ -447,7 +496,8 @@ int ilqg_solver_get_expected(ilqg_solver* s, double* dV, int* first_bad);
      While the nominal cost is invalid the choice is the plain selection's,
      unconditionally, and mu stays; it is invalid after enabling the mode and
      after ilqg_solver_init, set_traj, set_dinit, set_gains,
-     set_cost_schedule and shift_cost_schedule.
+     set_cost_schedule, shift_cost_schedule (and their _seeds forms) and
+     shift_horizon; ilqg_solver_refresh_nominal makes it valid again.
    - ilqg_backward (and the one inside ilqg_iterate) reads mu[s].  A step that
      is indefinite by the STANDARD test raises mu (the increase) and restarts
      the recursion from step 1, from the same V0, v0 (ilqg_solver_set_value's
